@@ -19,12 +19,25 @@ One step (BASELINE config 3, per rank = per robot):
          cslam_topk_merge_dev picks the exact whole-bank top-5; `sharded_check` compares one step with a single-GPU search
          of the whole bank.  --shard-mode robots: BASELINE config 4's shape, one full bank per rank (= per robot), top-5 for its own
          keyframes and best-1 for the other robots' keyframes
-value = keyframes processed by all ranks / max-over-ranks time of exactly K steps.
-The JSON line also carries: match_only / extract_only throughputs (the two legs timed separately), `roofline` (the candidate-stage
+value = keyframes processed by all ranks / max-over-ranks time of exactly K steps; ms_per_step = that time / K.
+
+A plain run sets up, warms up, times the K steps, writes the last step's outputs if --dump-outputs DIR is given and prints the
+headline line.  Everything else moves behind --full:
+
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full
+    python bench.py --gpus 1 --steps 3 --warmup 1 --dump-outputs DIR
+
+--dump-outputs DIR writes what the timed path returned for its last step, on rank 0: `descriptors` (the extracted keyframe
+descriptors; --no-extract: the query rows searched) and the search's `topk_rows` / `topk_sims` / `topk_count`, as DIR/<name>.npy in
+float32 / float64 (integers as float64).  Inputs are seeded, so two builds run with the same arguments can be compared array for
+array.  Past 64 MB in all, a fixed seeded sample of rows is written, its row numbers in DIR/<name>_sample_rows.npy.
+
+With --full, the JSON line also carries: match_only / extract_only throughputs (the two legs timed separately), `roofline` (the candidate-stage
 kernel's launches INSIDE the timed steps, HIP events on the launch stream), `roofline_c3_batch` (the separate 100k-query launch),
 `roofline_step_largest` (the trunk's pair products, from per-launch events of one-lane steps run after the timed region -- with two
 lanes a launch shares the chip with the other lane's kernels), `roofline_extract` (the other
-kernels of the extract leg on their real shapes) and `cpu_baseline` (the oracle restatements on a bounded sample).
+kernels of the extract leg on their real shapes), `cpu_baseline` (the oracle restatements on a bounded sample), `c2_cosplace`, the
+fp32-GEMM step, the measured peaks, the board sensors over the timed steps and, at N > 1 in rows mode, `sharded_check`.
 """
 import argparse
 import glob
@@ -236,7 +249,52 @@ def parse():
     ap.add_argument("--debug-shared-gpu", action="store_true",
                     help="debug only: all ranks share cuda:0 and exchange descriptors through gloo/CPU, to "
                          "exercise the N>1 control flow on a 1-GPU box (numbers are meaningless)")
-    return ap.parse_args()
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline: the legs timed separately, rooflines, measured "
+                         "peaks, board sensors, the fp32-GEMM step, cpu_baseline, c2_cosplace and (N > 1, rows) sharded_check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs (descriptors, top-k rows / sims / counts) as DIR/<name>.npy")
+    a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
+    return a
+
+
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, desc, match):
+    """The last timed step's outputs as path/<name>.npy: float32 / float64 kept, other floats as float32, integers as float64
+    (exact: row numbers and counts are far below 2**53).  Past DUMP_BUDGET_BYTES in all, every array keeps the same fixed seeded
+    sample of its rows, whose row numbers go to path/<name>_sample_rows.npy."""
+    import torch
+    arrays = [("descriptors", desc)]
+    if isinstance(match, (tuple, list)) and len(match) == 3 and all(torch.is_tensor(t) for t in match):
+        arrays += list(zip(("topk_rows", "topk_sims", "topk_count"), match))
+    else:                                            # N > 1, robots mode: (intra triple, inter tuple)
+        def walk(x, name):
+            if torch.is_tensor(x):
+                arrays.append((name, x))
+            elif isinstance(x, (tuple, list)):
+                for i, y in enumerate(x):
+                    walk(y, "%s_%d" % (name, i))
+        walk(match, "match")
+    host = []
+    for name, t in arrays:
+        x = t.detach().cpu().numpy()
+        if x.dtype not in (np.float32, np.float64):
+            x = x.astype(np.float64 if x.dtype.kind in "iub" else np.float32)
+        host.append((name, x))
+    total = sum(x.nbytes for _, x in host)
+    os.makedirs(path, exist_ok=True)
+    for name, x in host:
+        if total > DUMP_BUDGET_BYTES and x.ndim and x.shape[0] > 1:
+            n = x.shape[0]
+            keep = max(1, int(n * DUMP_BUDGET_BYTES * 0.9 / total))
+            rows = np.sort(np.random.default_rng(0).choice(n, keep, replace=False))
+            x = x[rows]
+            np.save(os.path.join(path, name + "_sample_rows.npy"), rows.astype(np.float64))
+        np.save(os.path.join(path, name + ".npy"), np.ascontiguousarray(x))
 
 
 def self_launch(a):
@@ -303,7 +361,9 @@ def main():
         bank_f = pool.submit(lambda: whole_np.result()[offs[rank]:offs[rank + 1]])
     else:
         bank_f = pool.submit(synthetic.bank, rank, local_rows, a.dim)
-    mq_f = pool.submit(synthetic.queries, rank, a.match_queries, a.dim)      # the match-only leg's queries (and --no-extract's)
+    mq_f = None
+    if a.full or a.no_extract:                                                # the match-only leg's queries (and --no-extract's)
+        mq_f = pool.submit(synthetic.queries, rank, a.match_queries, a.dim)
     bank = torch.from_numpy(bank_f.result()).to(dev)
     nn = nnm.NearestNeighborsMatching(device=local_rank)
     nn.add_items_device(bank)
@@ -314,7 +374,7 @@ def main():
                              "frontend.backbone_conv": a.backbone_conv}, None)
     bdt = None if a.backbone_dtype == "fp32" else torch.bfloat16
     frames = torch.from_numpy(synthetic.frames(rank * a.batch, a.batch)).to(dev)     # frame i of the job = default_rng(7 + i)
-    mq_all = torch.from_numpy(mq_f.result()).to(dev)
+    mq_all = None if mq_f is None else torch.from_numpy(mq_f.result()).to(dev)
     pool.shutdown()
     noext_pos = [0]
     if extractor is not None:
@@ -367,14 +427,15 @@ def main():
     pending = []
     side = torch.cuda.Stream(device=dev) if world > 1 else None     # N > 1: the matcher's stream (beside the next extraction)
     waiting = []                                                    # N > 1: (descriptors, ready event) of the step whose matching is next
+    last = {}                                                       # the latest step's descriptors and finished search (--dump-outputs)
 
     def retire():
         while pending:
             if side is not None:
                 with torch.cuda.stream(side):
-                    pending.pop(0).finish()
+                    last["match"] = pending.pop(0).finish()
             else:
-                pending.pop(0).finish()
+                last["match"] = pending.pop(0).finish()
             kernel_ms.append(nn.last_kernel_ms())      # events of a search that has finished: no wait
 
     def launch_match():
@@ -386,6 +447,7 @@ def main():
 
     def step():
         d = extract()                                  # enqueued; the host runs ahead of the GPU
+        last["desc"] = d
         retire()                                       # step i - 1's search: done long ago, its count is on the host
         if world == 1:
             pending.append(nn.search_device_async(d, a.k, mode=nnm.MODE_MFMA))
@@ -446,17 +508,60 @@ def main():
         _clib.check(_clib.load().cslam_trunk_timing(0))
         return [float(x) for x in tt]
     one_lane = extractor is None or a.extract_lanes <= 1 or bdt is not None
-    if extractor is not None and one_lane:
+    if a.full and extractor is not None and one_lane:
         _clib.check(_clib.load().cslam_trunk_timing(1))       # two HIP events per product launch, on the launch stream
-    sensors = BoardSensors(torch, dev.index or 0) if rank == 0 else None
+    sensors = BoardSensors(torch, dev.index or 0) if rank == 0 and a.full else None
     if sensors is not None:
         sensors.start()
     dt = timed(step, a.steps)
     board = sensors.finish() if sensors is not None else None
-    if extractor is not None and one_lane:
+    if a.full and extractor is not None and one_lane:
         trunk_times = read_trunk_times()
     step_kernel_ms = [m for m in kernel_ms if m > 0]
     value = world * a.batch * a.steps / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last["desc"], last["match"])
+    split16 = "128"
+    line = {
+        "metric": "keyframes/sec (extract+match) on 100kx4096-D bank",
+        "value": round(value, 2), "unit": "keyframes/sec", "n_gpus": world, "steps": a.steps,
+        "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
+        "scaling": "weak", "vs_baseline": None, "dtype": "f32" if bdt is None else "bf16 backbone / f32 heads+match",
+        "data": "synthetic (seeded on-device uint8 640x480 frames, unit-norm Gaussian bank, random-init "
+                "VGG-16/VLAD/PCA weights: the reference ships no checkpoints)",
+        "note": "north_star's 100k keyframes/s is above what one MI355X can extract on C3 at fp32-grade arithmetic: roofline_step.fp32_grade_ceiling "
+                "of a --full run (c2_cosplace is the configuration where it is arithmetically within reach)",
+        "config": {"workload": "C3: NetVLAD VGG-16 4096-D extract + D.D^T MFMA similarity + top-5, "
+                               f"{a.bank_rows}-row bank" + (" per GPU" if not rows_mode else "") + ("" if extractor else " [match leg only]"),
+                   "bank_rows": a.bank_rows, "dim": a.dim, "keyframes_per_rank_per_step": a.batch, "k": a.k,
+                   "queries_per_rank_per_step": world * a.batch if world > 1 else a.batch,
+                   "extract_chunk": a.extract_chunk, "extract_lanes": a.extract_lanes if extractor is not None else None,
+                   "bank_rows_per_gpu": local_rows,
+                   "parallelism": ("single GPU" if world == 1 else
+                                   "one %d-row bank split by rows over %d GPUs: RCCL all-gather of the new descriptors, "
+                                   "local top-k, all-to-all of the lists, HIP merge" % (a.bank_rows, world) if rows_mode
+                                   else "1 robot bank per GPU, RCCL all-gather of new descriptors")},
+        "full": a.full,
+        "ranks": world, "collective_backend": None if world == 1 else ("gloo via host (debug)" if a.debug_shared_gpu else "nccl (RCCL)"),
+        "backbone_conv": None if extractor is None else extractor.backbone_conv,
+        "trunk_gemm": None if extractor is None or extractor.backbone_conv != "winograd" else (
+            "plain fp32 (rocBLAS sgemm)" if split16 == "0" else
+            "conv3_1 ... conv5_3: F(4x4) Winograd with this library's GEMM (csrc/wino_gemm.hip) over exact fp16 hi/lo "
+            "pairs of both operands, 3 of the 4 partial products on the fp16 MFMA pipe with fp32 accumulation (error vs "
+            "float64 = that of the fp32 GEMM, tests/test_heads_gpu.py::test_split16_*, tests/test_wino_gemm_gpu.py); "
+            "conv1_1 + conv1_2: ONE direct kernel on fp16 pairs, the second layer's weights register-resident "
+            "(csrc/conv_stem_direct_h.hip); conv2_1: the same form (csrc/conv_direct_r.hip); conv2_2: the same form on "
+            "output-channel halves, two workgroups per block (csrc/conv_direct_r.hip, round 6)"),
+    }
+    if a.dump_outputs:
+        line["outputs_dir"] = os.path.abspath(a.dump_outputs)
+    if not a.full:
+        # a plain run: the headline only (every other measurement and check is behind --full)
+        if rank == 0:
+            print(json.dumps(line))
+        if world > 1:
+            dist.destroy_process_group()
+        return
     if extractor is not None and not one_lane:
         # with two lanes a product launch shares the chip with the other lane's kernels and its duration is not its own: the
         # per-launch figures of the trunk's products come from two one-lane steps run after the timed region
@@ -502,7 +607,6 @@ def main():
     # the same leg AND the same whole step with the trunk's GEMMs as plain fp32 (rocBLAS sgemm) instead of the default
     # split-fp16 pairs (fp32-grade either way): reported beside `extract_only` / `value`, N = 1 only
     extract_fp32_gemms = value_fp32_gemms = None
-    split16 = "128"
     if extractor is not None and world == 1 and extractor.backbone_conv == "winograd":
         from cslam_amd.vpr.winograd import FP32_GEMM_FORMS       # library sgemm between the transforms, conv1_2 / conv2_1 on the f32-input MFMA,
         ex32 = NetVLAD({"frontend.nn_checkpoint": "random", "frontend.image_crop_size": 376,          # conv1_1 as its own fp32 kernel
@@ -980,39 +1084,11 @@ def main():
                           "(profiles/r06_d_power_dp.json: ResNet layer1's kernel 1399 W of 1400 at 1.87 GHz; its matrix work alone 1315 W at 2.0 GHz), so its time "
                           "is its energy / the cap; a whole VGG pass, with its HBM-bound transforms and launch tails, averages below the cap: DESIGN.md section 8"}
     if rank == 0:
-        line = {
-            "metric": "keyframes/sec (extract+match) on 100kx4096-D bank",
-            "value": round(value, 2), "unit": "keyframes/sec", "n_gpus": world, "steps": a.steps,
-            "warmup": a.warmup, "ms_per_step": round(dt / a.steps * 1e3, 3), "higher_is_better": True,
-            "scaling": "weak", "vs_baseline": None, "dtype": "f32" if bdt is None else "bf16 backbone / f32 heads+match",
-            "data": "synthetic (seeded on-device uint8 640x480 frames, unit-norm Gaussian bank, random-init "
-                    "VGG-16/VLAD/PCA weights: the reference ships no checkpoints)",
-            "note": "north_star's 100k keyframes/s is above what one MI355X can extract on C3 at fp32-grade arithmetic: roofline_step.fp32_grade_ceiling "
-                    "(c2_cosplace is the configuration where it is arithmetically within reach)",
-            "config": {"workload": "C3: NetVLAD VGG-16 4096-D extract + D.D^T MFMA similarity + top-5, "
-                                   f"{a.bank_rows}-row bank" + (" per GPU" if not rows_mode else "") + ("" if extractor else " [match leg only]"),
-                       "bank_rows": a.bank_rows, "dim": a.dim, "keyframes_per_rank_per_step": a.batch, "k": a.k,
-                       "queries_per_rank_per_step": nq_step,
-                       "extract_chunk": a.extract_chunk, "extract_lanes": a.extract_lanes if extractor is not None else None,
-                       "bank_rows_per_gpu": local_rows,
-                       "parallelism": ("single GPU" if world == 1 else
-                                       "one %d-row bank split by rows over %d GPUs: RCCL all-gather of the new descriptors, "
-                                       "local top-k, all-to-all of the lists, HIP merge" % (a.bank_rows, world) if rows_mode
-                                       else "1 robot bank per GPU, RCCL all-gather of new descriptors")},
+        line.update({
             "sharded_check": sharded_check,
-            "ranks": world, "collective_backend": None if world == 1 else ("gloo via host (debug)" if a.debug_shared_gpu else "nccl (RCCL)"),
             "value_fp32_gemms": None if value_fp32_gemms is None else round(value_fp32_gemms, 2),
             "peaks_measured": peaks,
             "extract_only": None if extract_only is None else round(extract_only, 2),
-            "backbone_conv": None if extractor is None else extractor.backbone_conv,
-            "trunk_gemm": None if extractor is None or extractor.backbone_conv != "winograd" else (
-                "plain fp32 (rocBLAS sgemm)" if split16 == "0" else
-                "conv3_1 ... conv5_3: F(4x4) Winograd with this library's GEMM (csrc/wino_gemm.hip) over exact fp16 hi/lo "
-                "pairs of both operands, 3 of the 4 partial products on the fp16 MFMA pipe with fp32 accumulation (error vs "
-                "float64 = that of the fp32 GEMM, tests/test_heads_gpu.py::test_split16_*, tests/test_wino_gemm_gpu.py); "
-                "conv1_1 + conv1_2: ONE direct kernel on fp16 pairs, the second layer's weights register-resident "
-                "(csrc/conv_stem_direct_h.hip); conv2_1: the same form (csrc/conv_direct_r.hip); conv2_2: the same form on "
-                "output-channel halves, two workgroups per block (csrc/conv_direct_r.hip, round 6)"),
             "extract_only_fp32_gemms": None if extract_fp32_gemms is None else round(extract_fp32_gemms, 2),
             "match_only": round(match_only, 2),
             "match_only_queries": nqm,
@@ -1025,7 +1101,7 @@ def main():
             "cpu_baseline": cpu,
             "c2_cosplace": c2,
             "board": board,
-        }
+        })
         print(json.dumps(line))
     if world > 1:
         dist.destroy_process_group()

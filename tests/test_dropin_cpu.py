@@ -1,9 +1,8 @@
 """cslam_amd.dropin: the ten reference module names resolve to this package, with cslam itself unedited.
 
-Two layers: (1) everywhere (also on the GPU box, where the reference checkout does not exist): a stand-in EMPTY `cslam`
-package tree -- directories with empty __init__.py, no reference code -- proves that both install() forms map every
-name of `_MAP`; (2) in the build container only: the reference's own test files run unmodified through the
-start-up shim (tools/ref_dropin_proof.py).
+A stand-in EMPTY `cslam` package tree -- directories with empty __init__.py, no reference code -- proves that both
+install() forms and the start-up shim map every name of `_MAP`.  Running the reference's own test files through the shim
+needs a checkout of the reference beside this repository: tools/ref_dropin_proof.py does that by hand.
 """
 import os
 import subprocess
@@ -12,7 +11,6 @@ import sys
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-REF = "/root/reference"
 
 _CHECK = r"""
 import importlib, sys
@@ -76,17 +74,3 @@ def test_shim_can_be_switched_off(tmp_path):
             "print('none' if s is None else s.origin)")
     r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, cwd=standin)
     assert r.returncode == 0 and r.stdout.strip() == "none", r.stdout + r.stderr
-
-
-@pytest.mark.skipif(not os.path.isdir(os.path.join(REF, "tests")), reason="reference checkout only exists in the build container")
-def test_reference_unit_tests_pass_unmodified_through_the_shim():
-    sys.path.insert(0, os.path.join(ROOT, "tools"))
-    try:
-        import ref_dropin_proof
-    finally:
-        sys.path.pop(0)
-    ok, out, routed = ref_dropin_proof.run(gpu=False)
-    assert ok, out[-4000:]
-    assert "18 passed" in out
-    assert any("cslam.algebraic_connectivity_maximization -> cslam_amd." in ln for ln in routed)
-    assert any("cslam.broker -> cslam_amd." in ln for ln in routed)

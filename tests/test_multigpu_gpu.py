@@ -191,7 +191,7 @@ def test_bench_self_launch_over_rccl(mode):
     import subprocess
     n = min(N_GPUS, 8)
     env = dict(os.environ, HSA_ENABLE_IPC_MODE_LEGACY="0")
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1",
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--full",
                         "--no-cpu-baseline", "--bank-rows", "40000", "--batch", "512", "--match-queries", "4096", "--shard-mode", mode],
                        capture_output=True, text=True, env=env, timeout=1500, cwd=ROOT)
     assert r.returncode == 0, r.stderr[-3000:]

@@ -7,8 +7,8 @@ python -c "import __graft_entry__ as g; g.smoke(); print('smoke ok')" > $O/smoke
 if [ "${2:-}" != "notests" ]; then
   timeout 1500 python -m pytest tests -q -m gpu --durations=15 > $O/tests_gpu.log 2>&1; tail -22 $O/tests_gpu.log
 fi
-python bench.py > $O/bench.json 2> $O/bench.err; tail -c 200 $O/bench.err; tail -c 1500 $O/bench.json | head -c 400; echo
-timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python bench.py --no-cpu-baseline --no-c2 > $O/prof_bench.json 2> $O/prof.err
+python bench.py --full > $O/bench.json 2> $O/bench.err; tail -c 200 $O/bench.err; tail -c 1500 $O/bench.json | head -c 400; echo
+timeout 900 rocprofv3 --kernel-trace --stats --output-format csv -d $O/prof -o b -- python bench.py --full --no-cpu-baseline --no-c2 > $O/prof_bench.json 2> $O/prof.err
 f=$(find $O/prof -name "*kernel_stats.csv" | head -1); [ -n "$f" ] && cp $f $O/kernel_stats.csv
 python - $O/kernel_stats.csv > $O/kernel_stats.txt <<'PY'
 import csv, sys

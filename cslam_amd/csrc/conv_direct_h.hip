@@ -30,6 +30,7 @@
 #include <type_traits>
 #include <hip/hip_fp16.h>
 #include "common.h"
+#include "pairs.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -41,7 +42,8 @@ typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 #define CD_WROWB 128                   // bytes per weight row of a stage: [hi 32 | lo 32]
 #define CD_WSTAGE (128 * CD_WROWB)     // 16 KB: 128 output channels
 #define CD_NW 3                        // weight stages in the ring: requests run two stages ahead
-#define CD_LDS (2 * CD_PATCHB + CD_NW * CD_WSTAGE + 512 + 256)  // + the 128 bias values + a sink for the patch elements that do not exist
+#define CD_SINKB 256
+#define CD_LDS (2 * CD_PATCHB + CD_NW * CD_WSTAGE + 512 + CD_SINKB)  // + the 128 bias values + a sink for the patch elements that do not exist
 
 struct ConvDirectArgs {
     const float *x; const char *w2; const float *bias; float *y;
@@ -51,18 +53,6 @@ struct ConvDirectArgs {
     const unsigned *amax_in; float inv_sw; unsigned *amax_out;
     int stagger_cycles;                // start-up offset per phase (workgroup >> 3 & 3), 0 = none
 };
-
-// LDS-DMA in the MUBUF encoding (`buffer_load_dwordx4 ... lds`; sim_topk_pair.hip has the why: hipcc counts LDS reads again -- behind
-// a pending `global_load_lds` every lgkmcnt(N) became lgkmcnt(0) --, the stage's offset travels in an SGPR, the lane's in one register)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t cd_rsrc(const char *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a);
-    const int n = __builtin_amdgcn_readfirstlane((int)(bytes > 0x7fffffff ? 0x7fffffff : bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)u, 0, n, 0x00020000);
-}
-__device__ __forceinline__ void cd_blds16(__amdgpu_buffer_rsrc_t rs, int voff, int soff, char *lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)lds_wave_base, 16, voff, soff, 0, 0);
-}
 
 // DBG (builds with -DCSLAM_ABLATIONS only; WRONG results): 1 = no weight requests after the prologue, 2 = no patch staging after the
 // prologue, 3 = both; + 4 = no stage barrier / wait; + 8 = fragments read once per workgroup only; 32 = patch loaded but not split into
@@ -91,16 +81,6 @@ __device__ __forceinline__ float cd_pool4(float v) {
     return v;
 }
 
-// v - (float)half HI of the packed pair h: one v_fma_mix_f32, the fp16 operand read in place (conv_stem_direct_h.hip's sd_sub_half)
-template <int HI>
-__device__ __forceinline__ float cd_sub_half(float v, __half2 h) {
-    float d;
-    const unsigned hb = *(const unsigned *)&h;
-    if (HI) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    return d;
-}
-
 // XP: x is a PAIR-FORMAT map (conv_igemm.hip: [pixel][32-channel block][hi 32 | lo 32] fp16 of s x; amax_in = its BOUND slot, which fixes
 // s).  A pixel's slab is the same 128 bytes at the same address as in a float32 map, so the loads do not change; an element is one of
 // its eight 16-byte chunks and goes to LDS as it is -- the split (two packed conversions, four v_fma_mix, two more conversions per
@@ -120,11 +100,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_direct_h_kernel(ConvDirectArgs
     const int h = lane >> 5, l31 = lane & 31;
     if (tid < 128) s_bias[tid] = p.bias ? p.bias[tid] : 0.0f;   // visible behind the prologue's barrier
 
-    // power-of-two input scale: max |x| s_x <= 2^15 - 16 (fp16 holds 65504; the products stay far inside fp32)
-    const float amax = fminf(fmaxf(__uint_as_float(*p.amax_in), 1e-30f), 1e30f);
-    int e_;
-    (void)frexpf(XP ? amax : 32752.0f / amax, &e_);
-    const float sx = XP ? ldexpf(1.0f, 14 - e_) : ldexpf(1.0f, e_ - 1);        // XP: the producer's scale (conv_igemm.hip::ci_scale of the bound)
+    // power-of-two input scale (XP: the producer's, from the bound)
+    const float amax = __uint_as_float(*p.amax_in);
+    const float sx = XP ? scale_in_2p13_2p14(amax) : scale_le_32752(amax);
     const float inv = p.inv_sw / sx;
 
     // Blocks to workgroups, XCD-aware (as conv_stem_direct_h.hip): workgroup w runs on XCD w % 8, every XCD has its own L2; each XCD
@@ -171,6 +149,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_direct_h_kernel(ConvDirectArgs
         validpack |= (valid ? 1u : 0u) << i;
     }
     char *const s_sink = cd_smem + 2 * CD_PATCHB + CD_NW * CD_WSTAGE + 512 + (tid & 15) * (XP ? 16 : 8);
+    static_assert(15 * (XP ? 16 : 8) + (XP ? 16 : 64 + 8) <= CD_SINKB, "a sink store leaves the sink");   // (XP: 16 bytes; else hi 8, lo 8 at + 64)
     // block coordinates are decoded ONCE per block on the scalar unit (three run-time divisions: ~90 dependent scalar instructions,
     // which sat at the top of two stages per slab): `cb` = the block being multiplied, `nb` = the next one (the last block again
     // behind the workgroup's last)
@@ -196,7 +175,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_direct_h_kernel(ConvDirectArgs
         // (vmcnt(NV)), and a load under `if (inside)` is skipped by waves whose lanes are all outside (s_cbranch_execz) -- such a
         // wave then waited for fewer of its OLDER requests than it had to, and with the weights slow to arrive (another stream
         // thrashing the L2) multiplied a ring slot that had not landed (round 4's first form)
-        const __amdgpu_buffer_rsrc_t rsX = cd_rsrc(b.xb, img_bytes);
+        const __amdgpu_buffer_rsrc_t rsX = buf_rsrc(b.xb, img_bytes, RSRC_LIM);
         const int blk_off = ((b.by * 16 - 1) * p.W + (b.bx * 16 - 1)) * p.Cin * 4;
         const int gx0 = b.bx * 16 - 1;
         unsigned m = inmask & ~(7u << (3 * half));
@@ -231,8 +210,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_direct_h_kernel(ConvDirectArgs
             const __half2 h01 = __floats2half2_rn(w0, w1), h23 = __floats2half2_rn(w2, w3);
             // w - (float)hi straight out of the packed register (v_fma_mix_f32; through __half22float2 hipcc rounds every value a second
             // time with a scalar v_cvt_f16_f32, converts that back and subtracts: three instructions per value instead of one)
-            const __half2 l01 = __floats2half2_rn(cd_sub_half<0>(w0, h01), cd_sub_half<1>(w1, h01));
-            const __half2 l23 = __floats2half2_rn(cd_sub_half<0>(w2, h23), cd_sub_half<1>(w3, h23));
+            const __half2 l01 = __floats2half2_rn(sub_half<0>(w0, h01), sub_half<1>(w1, h01));
+            const __half2 l23 = __floats2half2_rn(sub_half<0>(w2, h23), sub_half<1>(w3, h23));
             char *d = pd >= 0 ? dst + pd : s_sink;
             *(uint2 *)d = make_uint2(*(const unsigned *)&h01, *(const unsigned *)&h23);
             *(uint2 *)(d + 64) = make_uint2(*(const unsigned *)&l01, *(const unsigned *)&l23);
@@ -242,7 +221,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_direct_h_kernel(ConvDirectArgs
     // ---- weight loader: chunk pch = i * 512 + tid -> row pch >> 3 (output channel), physical 16-byte slot pch & 7 holding
     // logical chunk slot ^ ((row >> 1) & 7) of the row's 128-byte block (wino_gemm.hip's image: conflict-free ds_read_b128)
     const int tap_stride = 128 * p.nslab * CD_WROWB;
-    const __amdgpu_buffer_rsrc_t rsW = cd_rsrc(p.w2, (int64_t)9 * tap_stride);
+    const __amdgpu_buffer_rsrc_t rsW = buf_rsrc(p.w2, (int64_t)9 * tap_stride, RSRC_LIM);
     int voffW[2];                                              // the lane's two chunks inside a (tap, slab)'s 128 rows
 #pragma unroll
     for (int i = 0; i < 2; ++i) {
@@ -329,7 +308,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_direct_h_kernel(ConvDirectArgs
 #pragma unroll
     for (int b = 0; b < 2; ++b) {                              // stages 0 and 1: (tap 0 | 1, slab 0); the offset moves on to (tap 2, slab 0)
 #pragma unroll
-        for (int i = 0; i < 2; ++i) cd_blds16(rsW, voffW[i], woff, s_w + b * CD_WSTAGE + wave * 1024 + i * (512 * 16));
+        for (int i = 0; i < 2; ++i) buf_lds16(rsW, voffW[i], woff, s_w + b * CD_WSTAGE + wave * 1024 + i * (512 * 16));
         woff += tap_stride;
     }
     patch_load(cb, 0, 0); patch_store(0, 0, 0, NPL / 2);
@@ -371,7 +350,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_direct_h_kernel(ConvDirectArgs
             const int wb2 = wb == 0 ? 2 : wb - 1;
             char *d = s_w + wb2 * CD_WSTAGE + wave * 1024;
 #pragma unroll
-            for (int i = 0; i < 2; ++i) cd_blds16(rsW, voffW[i], woff, d + i * (512 * 16));
+            for (int i = 0; i < 2; ++i) buf_lds16(rsW, voffW[i], woff, d + i * (512 * 16));
             // a RUNNING offset (scalar): written as (TAP + 1) * tap_stride + ... the nine taps' addresses are loop invariants that the
             // compiler keeps in registers across the K loop (as 64-bit per-lane pointers, round 4's first form: 36 VGPRs, the kernel
             // spilled).  Behind tap 6's request -- tap 8 of this slab -- comes tap 0 of the next slab: a relative step.

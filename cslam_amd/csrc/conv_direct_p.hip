@@ -28,6 +28,7 @@
 #include <type_traits>
 #include <hip/hip_fp16.h>
 #include "common.h"
+#include "pairs.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -50,34 +51,6 @@ struct ConvDirectPArgs {
     int relu;
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t dp_rsrc(const char *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a);
-    const int n = __builtin_amdgcn_readfirstlane((int)(bytes > 0x7ffffff0ll ? 0x7ffffff0ll : bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)u, 0, n, 0x00020000);
-}
-// (a __device__ function, not the builtin inside the kernel's lambda: conv_igemm.hip)
-__device__ __forceinline__ void dp_blds16(__amdgpu_buffer_rsrc_t rs, int voff, char *lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)lds_wave_base, 16, voff, 0, 0, 0);
-}
-__device__ __forceinline__ float dp_scale(unsigned amax_bits) {            // conv_igemm.hip::ci_scale
-    const float a = fminf(fmaxf(__uint_as_float(amax_bits), 1e-30f), 1e30f);
-    int e;
-    (void)frexpf(a, &e);
-    return ldexpf(1.0f, 14 - e);
-}
-typedef _Float16 f16x2 __attribute__((ext_vector_type(2)));
-// (float)half HI of hb * s + v: hipcc selects ONE v_fma_mix_f32 for this (as inline assembly the scheduler cannot place it: a
-// sched_group_barrier pipeline leaves every asm statement of a region behind the region's last MFMA)
-template <int HI>
-__device__ __forceinline__ float dp_fma_half(unsigned hb, float s, float v) {
-    return __builtin_fmaf((float)__builtin_bit_cast(f16x2, hb)[HI], s, v);
-}
-__device__ __forceinline__ unsigned dp_pk(float a, float b) {              // (fp16 rn(a), fp16 rn(b)) in one dword
-    const __half2 h = __floats2half2_rn(a, b);
-    return *(const unsigned *)&h;
-}
-
 // RES: shortcut 0 none, 1 float32 NHWC, 2 pair format; OUTP: y in pair format (else float32 NHWC)
 // DBG (builds with -DCSLAM_ABLATIONS only; WRONG results, timing): 1 no epilogue, 2 no patch requests inside the loop, 4 no shortcut loads,
 // 8 no fragment reads after a block's first two, 16 no stores (the epilogue's arithmetic stays)
@@ -91,6 +64,8 @@ __device__ __forceinline__ unsigned dp_pk(float a, float b) {              // (f
 template <int RES, bool OUTP, int NRW, int DBG = 0, bool XF32 = false>
 __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDirectPArgs p) {
     constexpr int NW = 32 / NRW, NPR = NRW + 2, NDMA = DP_NDMA(NW), PATCHB = DP_PATCHB(NW);
+    // the sinks behind the 50 KB patch: DMA pieces 50 .. (1 KB each at 1 KB j); XF32, a lane's element (hi 8 bytes at 16 (lane & 63), lo at ^ 64)
+    static_assert(2 * DP_HALFB == 50 * 1024 && NW * NDMA * 1024 <= PATCHB && 2 * DP_HALFB + 63 * 16 + 64 + 8 <= PATCHB, "a sink store leaves the buffer");
     extern __shared__ __attribute__((aligned(16))) char dp_smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -99,17 +74,17 @@ __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDir
     const int gq = lane >> 4, l15 = lane & 15;
     const int lh = l15 >> 3, l7 = l15 & 7;                     // the lane's half-block and pixel column inside it
 
-    const float sc = dp_scale(XF32 ? *p.amax_in : *p.xbound);
+    const float sc = scale_in_2p13_2p14(__uint_as_float(XF32 ? *p.amax_in : *p.xbound));
     const float inv = p.inv_sw / sc;
     float s_out = 1.0f, inv_sres = 0.0f;
     if (OUTP) {
         const float xmax = __uint_as_float(*p.amax_in);
         const float rmax = RES ? __uint_as_float(*p.res_bound) : 0.0f;
         const float bound = (xmax * p.wl1 + p.bmax + rmax) * 1.001f;       // >= max |y| whatever the rounding of the products
-        s_out = dp_scale(__float_as_uint(bound));
+        s_out = scale_in_2p13_2p14(bound);
         if (blockIdx.x == 0 && tid == 0) *p.bound_out = __float_as_uint(bound);
     }
-    if (RES == 2) inv_sres = 1.0f / dp_scale(*p.res_bound);
+    if (RES == 2) inv_sres = 1.0f / scale_in_2p13_2p14(__uint_as_float(*p.res_bound));
     const float floor_ = p.relu ? 0.0f : -INFINITY;
     float neg1 = -1.0f;                                        // (a run-time value: with the literal hipcc folds fma(h, -1, u) into a conversion and a subtraction)
     asm volatile("" : "+v"(neg1));
@@ -180,7 +155,7 @@ __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDir
         st_by = t + (n & p.gyb);
         st_img += step_img + 1 + n;
     };
-    auto rsrc_of = [&](const char *base, const Blk &b) { return dp_rsrc(base + b.ioff, b.range); };
+    auto rsrc_of = [&](const char *base, const Blk &b) { return buf_rsrc(base + b.ioff, b.range, RSRC_LIM16); };
 
     // ---- patch requests: instruction i of this wave = DMA piece j = 4 i + wave: half j / 25, its pixels 4 (j % 25) .. + 3 (patch row
     // major, 10 per row); lane -> pixel (lane >> 4) of the four, physical slot lane & 15 = logical 16-byte chunk ^ (2 c & 15)
@@ -206,7 +181,7 @@ __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDir
         asm volatile("" : "+v"(rel));                          // (pins the request's arithmetic to its region: hipcc otherwise gathers all thirteen in front of the first)
         const int off = org + rel;
         const bool in = ((unsigned)(by8 + dm_r[I]) < (unsigned)p.H) & ((unsigned)(bx8 + dm_c[I]) < (unsigned)p.W);
-        dp_blds16(rsX, in ? off : DP_OOB, npatch + j * 1024);
+        buf_lds16(rsX, in ? off : DP_OOB, 0, npatch + j * 1024);
     };
 
     // ---- XF32: the patch through registers.  Element e = i * 256 + tid = (patch pixel e >> 4 of the 2 x 100, channels 4 (e & 15) .. + 3)
@@ -240,9 +215,9 @@ __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDir
         u32x4 v = stg[I];
         asm volatile("" : "+v"(v));
         const float w0 = __uint_as_float(v.x) * sc, w1 = __uint_as_float(v.y) * sc, w2 = __uint_as_float(v.z) * sc, w3 = __uint_as_float(v.w) * sc;
-        const unsigned h01 = dp_pk(w0, w1), h23 = dp_pk(w2, w3);
-        const unsigned l01 = dp_pk(dp_fma_half<0>(h01, neg1, w0), dp_fma_half<1>(h01, neg1, w1));
-        const unsigned l23 = dp_pk(dp_fma_half<0>(h23, neg1, w2), dp_fma_half<1>(h23, neg1, w3));
+        const unsigned h01 = pack_half2(w0, w1), h23 = pack_half2(w2, w3);
+        const unsigned l01 = pack_half2(fma_half<0>(h01, neg1, w0), fma_half<1>(h01, neg1, w1));
+        const unsigned l23 = pack_half2(fma_half<0>(h23, neg1, w2), fma_half<1>(h23, neg1, w3));
         char *d = npatch + sg_dst[I];
         *(u32x2 *)d = (u32x2){h01, h23};
         *(u32x2 *)(npatch + (sg_dst[I] ^ 64)) = (u32x2){l01, l23};      // (the lo halves: logical chunk + 4 = physical chunk ^ 4)
@@ -289,10 +264,10 @@ __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDir
         ev[0] = __builtin_fmaf(eacc[r][0], inv, bv.x); ev[1] = __builtin_fmaf(eacc[r][1], inv, bv.y);
         ev[2] = __builtin_fmaf(eacc[r][2], inv, bv.z); ev[3] = __builtin_fmaf(eacc[r][3], inv, bv.w);
         if (RES == 2) {
-            ev[0] = dp_fma_half<0>(rres[r].x, inv_sres, ev[0]); ev[1] = dp_fma_half<1>(rres[r].x, inv_sres, ev[1]);
-            ev[2] = dp_fma_half<0>(rres[r].y, inv_sres, ev[2]); ev[3] = dp_fma_half<1>(rres[r].y, inv_sres, ev[3]);
-            ev[0] = dp_fma_half<0>(rres[r].z, inv_sres, ev[0]); ev[1] = dp_fma_half<1>(rres[r].z, inv_sres, ev[1]);
-            ev[2] = dp_fma_half<0>(rres[r].w, inv_sres, ev[2]); ev[3] = dp_fma_half<1>(rres[r].w, inv_sres, ev[3]);
+            ev[0] = fma_half<0>(rres[r].x, inv_sres, ev[0]); ev[1] = fma_half<1>(rres[r].x, inv_sres, ev[1]);
+            ev[2] = fma_half<0>(rres[r].y, inv_sres, ev[2]); ev[3] = fma_half<1>(rres[r].y, inv_sres, ev[3]);
+            ev[0] = fma_half<0>(rres[r].z, inv_sres, ev[0]); ev[1] = fma_half<1>(rres[r].z, inv_sres, ev[1]);
+            ev[2] = fma_half<0>(rres[r].w, inv_sres, ev[2]); ev[3] = fma_half<1>(rres[r].w, inv_sres, ev[3]);
         } else if (RES == 1) {
             ev[0] += __uint_as_float(rres[r].x); ev[1] += __uint_as_float(rres[r].y); ev[2] += __uint_as_float(rres[r].z); ev[3] += __uint_as_float(rres[r].w);
         }
@@ -308,9 +283,9 @@ __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDir
         off = row0 + r < eo.rows ? off : DP_OOB;
         if (OUTP) {
             const float u0 = ev[0] * s_out, u1 = ev[1] * s_out, u2 = ev[2] * s_out, u3 = ev[3] * s_out;
-            const unsigned h01 = dp_pk(u0, u1), h23 = dp_pk(u2, u3);
-            const unsigned l01 = dp_pk(dp_fma_half<0>(h01, neg1, u0), dp_fma_half<1>(h01, neg1, u1));
-            const unsigned l23 = dp_pk(dp_fma_half<0>(h23, neg1, u2), dp_fma_half<1>(h23, neg1, u3));
+            const unsigned h01 = pack_half2(u0, u1), h23 = pack_half2(u2, u3);
+            const unsigned l01 = pack_half2(fma_half<0>(h01, neg1, u0), fma_half<1>(h01, neg1, u1));
+            const unsigned l23 = pack_half2(fma_half<0>(h23, neg1, u2), fma_half<1>(h23, neg1, u3));
             if (!(DBG & 16)) {
                 __builtin_amdgcn_raw_buffer_store_b64((u32x2){h01, h23}, rsY, off, 0, 0);
                 __builtin_amdgcn_raw_buffer_store_b64((u32x2){l01, l23}, rsY, off, 64, 0);

@@ -18,6 +18,7 @@
 #include <type_traits>
 #include <hip/hip_fp16.h>
 #include "common.h"
+#include "pairs.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -30,7 +31,10 @@ typedef float dr_f32x2 __attribute__((ext_vector_type(2)));
 #define DR_PATCHB (10 * DR_RP)         // 57 600 per buffer
 #define DR_NPIX 180
 #define DR_NEL 12                      // float4 elements per thread and patch: 180 pixels x 16 = 2880 <= 12 x 256
-#define DR_LDS (2 * DR_PATCHB + 4096)   // + a sink for the elements of the last staging round that do not exist (no branch around a store)
+#define DR_SINKB 4096
+#define DR_LDS (2 * DR_PATCHB + DR_SINKB)   // + a sink for the elements of the last staging round that do not exist (no branch around a store)
+// a staged element's stores: 8 bytes of hi halves at its destination, 8 of lo halves 128 bytes further; the sink of a lane is at 16 (lane & 63)
+#define DR_SINK_END (63 * 16 + 128 + 8)
 
 struct ConvDirectRArgs {
     const float *x; const f16x8 *w2; const float *bias; float *y;
@@ -40,12 +44,6 @@ struct ConvDirectRArgs {
     float wl1, bmax; unsigned *bound_out;          // OUTP: y leaves in pair format (conv_igemm.hip), scaled for the bound max|x| wl1 + bmax
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t dr_rsrc(const char *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a);
-    const int n = __builtin_amdgcn_readfirstlane((int)(bytes > 0x7ffffff0 ? 0x7ffffff0 : bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)u, 0, n, 0x00020000);
-}
 #ifdef CSLAM_ABLATIONS
 __device__ unsigned long long *dr_prof = nullptr;             // measurement build: [six columns (+ staging), epilogue, barrier, blocks] ticks of wave 0 / workgroup 0
 extern "C" __attribute__((visibility("default"))) int cslam_debug_dr_prof_dev(void *d_buf) {
@@ -56,54 +54,29 @@ extern "C" __attribute__((visibility("default"))) int cslam_debug_dr_prof_dev(vo
 #else
 #define DR_PROF 0
 #endif
-template <int HI>
-__device__ __forceinline__ float dr_sub_half(float v, __half2 h) {       // v - (float)half HI of h: one v_fma_mix_f32
-    float d;
-    const unsigned hb = *(const unsigned *)&h;
-    if (HI) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    return d;
-}
-__device__ __forceinline__ float dr_max(float a, float b) {
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-__device__ __forceinline__ float dr_max_xor1(float v) {                   // max(v, v of lane ^ 1): DPP quad permutation
-    const float a = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    return dr_max(v, a);
-}
 
 // DBG (builds with -DCSLAM_ABLATIONS only; WRONG results, timing): 1 = no patch staging inside the loop, 4 = no stores
 // OUTP (no pooling): y is written in the PAIR FORMAT of conv_igemm.hip -- [pixel][32-channel block][hi 32 | lo 32] fp16 of s y, s the
 // power of two that brings the bound max|x| wl1 + bmax (stored to bound_out) into [2^13, 2^14) -- so that the next layer (conv2_2,
 // conv_direct_h.hip) stages its patch without converting anything (0.34 of its 2.5 ms were the split's vector instructions)
-typedef _Float16 dr_f16x2 __attribute__((ext_vector_type(2)));
-template <int HI>
-__device__ __forceinline__ float dr_fma_half(unsigned hb, float s, float v) { return __builtin_fmaf((float)__builtin_bit_cast(dr_f16x2, hb)[HI], s, v); }
-__device__ __forceinline__ unsigned dr_pk(float a, float b) { const __half2 h = __floats2half2_rn(a, b); return *(const unsigned *)&h; }
 template <bool POOL, bool RELU, int DBG = 0, bool OUTP = false>
 __global__ __launch_bounds__(256, 1) void conv3x3_direct_r_kernel(ConvDirectRArgs p) {
     static_assert(!(POOL && OUTP), "the pair-format output is written un-pooled");
+    static_assert(DR_SINK_END <= DR_SINKB, "a sink store leaves the sink");
     extern __shared__ __attribute__((aligned(16))) char dr_smem[];
     const int tid = threadIdx.x;
     const int lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int gq = lane >> 4, l15 = lane & 15;
 
-    // power-of-two input scale: max |x| s_x <= 2^15 - 16
-    const float amax = fminf(fmaxf(__uint_as_float(*p.amax_in), 1e-30f), 1e30f);
-    int e_;
-    (void)frexpf(32752.0f / amax, &e_);
-    const float sx = ldexpf(1.0f, e_ - 1);
+    const float amax = fminf(fmaxf(__uint_as_float(*p.amax_in), 1e-30f), 1e30f);        // (for OUTP's bound: the scale clamps on its own)
+    const float sx = scale_le_32752(__uint_as_float(*p.amax_in));
     const float inv = p.inv_sw / sx;
     float s_out = 1.0f, neg1 = -1.0f;
     asm volatile("" : "+v"(neg1));                             // (a run-time -1: conv_direct_p.hip)
     if (OUTP) {
         const float bound = (amax * p.wl1 + p.bmax) * 1.001f;  // >= max |y| whatever the rounding of the products
-        int eo;
-        (void)frexpf(fminf(fmaxf(bound, 1e-30f), 1e30f), &eo);
-        s_out = ldexpf(1.0f, 14 - eo);                         // conv_igemm.hip::ci_scale
+        s_out = scale_in_2p13_2p14(bound);
         if (blockIdx.x == 0 && threadIdx.x == 0) *p.bound_out = __float_as_uint(bound);
     }
 
@@ -171,7 +144,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r_kernel(ConvDirectRArg
     // the image is the buffer: rows above and below it are out of its range and read as zero; columns left and right of it would read the
     // neighbouring row's pixels and are zeroed when the registers are split.  Every lane issues every load (no branch): counted waits.
     auto patch_load = [&](const Blk &b, int i) {
-        const __amdgpu_buffer_rsrc_t rsX = dr_rsrc((const char *)p.x + (int64_t)b.img * img_bytes, img_bytes);
+        const __amdgpu_buffer_rsrc_t rsX = buf_rsrc((const char *)p.x + (int64_t)b.img * img_bytes, img_bytes, RSRC_LIM16);
         const int blk_off = ((b.by * 8 - 1) * p.W + (b.bx * 16 - 1)) * 256;
         int t = tid;
         asm volatile("" : "+v"(t));                            // opaque: the twelve offsets are loop invariants otherwise, hoisted and spilled
@@ -191,7 +164,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r_kernel(ConvDirectRArg
         asm("" : "+v"(w01), "+v"(w23));                        // (used AS pairs: hipcc keeps the two v_pk_mul_f32)
         const float w0 = w01[0], w1 = w01[1], w2 = w23[0], w3 = w23[1];
         const __half2 h01 = __floats2half2_rn(w0, w1), h23 = __floats2half2_rn(w2, w3);
-        const float d0 = dr_sub_half<0>(w0, h01), d1 = dr_sub_half<1>(w1, h01), d2 = dr_sub_half<0>(w2, h23), d3 = dr_sub_half<1>(w3, h23);
+        const float d0 = sub_half<0>(w0, h01), d1 = sub_half<1>(w1, h01), d2 = sub_half<0>(w2, h23), d3 = sub_half<1>(w3, h23);
         const __half2 l01 = __floats2half2_rn(d0, d1), l23 = __floats2half2_rn(d2, d3);
         // (branch-free: a region must stay ONE basic block for its instruction order to be set; what does not exist goes to the sink)
         char *d = st_dst[i] >= 0 ? patch + st_dst[i] : dr_smem + 2 * DR_PATCHB + (tid & 63) * 16;
@@ -219,7 +192,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r_kernel(ConvDirectRArg
     const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
     Blk eb = {0, 0, 0};                                        // the block being multiplied
     auto epi_rows = [&](int k) {                               // POOL: pooled row k (output rows 2 k, 2 k + 1); else output row k
-        const __amdgpu_buffer_rsrc_t rsY = dr_rsrc((const char *)(p.y + (int64_t)eb.img * Ho * Wo * 128), (int64_t)Ho * Wo * 512);
+        const __amdgpu_buffer_rsrc_t rsY = buf_rsrc((const char *)(p.y + (int64_t)eb.img * Ho * Wo * 128), (int64_t)Ho * Wo * 512, RSRC_LIM16);
         const int ox = eb.bx * 16 + l15;
 #pragma unroll
         for (int mt = 0; mt < 2; ++mt) {
@@ -229,8 +202,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r_kernel(ConvDirectRArg
             int off;
             if (POOL) {
                 const int py = eb.by * 4 + k;
-                v.x = dr_max_xor1(dr_max(acc[2 * k][mt][0], acc[2 * k + 1][mt][0])); v.y = dr_max_xor1(dr_max(acc[2 * k][mt][1], acc[2 * k + 1][mt][1]));
-                v.z = dr_max_xor1(dr_max(acc[2 * k][mt][2], acc[2 * k + 1][mt][2])); v.w = dr_max_xor1(dr_max(acc[2 * k][mt][3], acc[2 * k + 1][mt][3]));
+                v.x = max_f32_xor1(max_f32(acc[2 * k][mt][0], acc[2 * k + 1][mt][0])); v.y = max_f32_xor1(max_f32(acc[2 * k][mt][1], acc[2 * k + 1][mt][1]));
+                v.z = max_f32_xor1(max_f32(acc[2 * k][mt][2], acc[2 * k + 1][mt][2])); v.w = max_f32_xor1(max_f32(acc[2 * k][mt][3], acc[2 * k + 1][mt][3]));
                 store = ((l15 & 1) == 0) & ((ox >> 1) < Wo) & (py < Ho);
                 off = (py * Wo + (ox >> 1)) * 512 + ch_off;
             } else {
@@ -241,15 +214,15 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r_kernel(ConvDirectRArg
             }
             v.x = v.x * inv + bv[mt].x; v.y = v.y * inv + bv[mt].y; v.z = v.z * inv + bv[mt].z; v.w = v.w * inv + bv[mt].w;
             if (RELU) { v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f); }
-            float m = dr_max(dr_max(fabsf(v.x), fabsf(v.y)), dr_max(fabsf(v.z), fabsf(v.w)));
+            float m = max_f32(max_f32(fabsf(v.x), fabsf(v.y)), max_f32(fabsf(v.z), fabsf(v.w)));
             asm volatile("" : "+v"(m), "+v"(off));             // (both computed by every lane: no branch around them)
-            my_amax = dr_max(my_amax, store ? m : 0.0f);
+            my_amax = max_f32(my_amax, store ? m : 0.0f);
             if (OUTP) {
                 // the lane's four channels 32 wave + 16 mt + 4 gq .. + 3 of the pixel: block `wave`, hi run at its halfs 16 mt + 4 gq, lo run 64 bytes on
                 const float u0 = v.x * s_out, u1 = v.y * s_out, u2 = v.z * s_out, u3 = v.w * s_out;
-                const unsigned h01 = dr_pk(u0, u1), h23 = dr_pk(u2, u3);
-                const unsigned l01 = dr_pk(dr_fma_half<0>(h01, neg1, u0), dr_fma_half<1>(h01, neg1, u1));
-                const unsigned l23 = dr_pk(dr_fma_half<0>(h23, neg1, u2), dr_fma_half<1>(h23, neg1, u3));
+                const unsigned h01 = pack_half2(u0, u1), h23 = pack_half2(u2, u3);
+                const unsigned l01 = pack_half2(fma_half<0>(h01, neg1, u0), fma_half<1>(h01, neg1, u1));
+                const unsigned l23 = pack_half2(fma_half<0>(h23, neg1, u2), fma_half<1>(h23, neg1, u3));
                 const int offp = store ? off - ch_off + wave * 128 + (16 * mt + 4 * gq) * 2 : 0x7fffffff;
                 typedef unsigned dr_u32x2 __attribute__((ext_vector_type(2)));
                 __builtin_amdgcn_raw_buffer_store_b64((dr_u32x2){h01, h23}, rsY, offp, 0, 0);
@@ -359,7 +332,11 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r_kernel(ConvDirectRArg
 // the kernel above (slab 0, slab 1; the accumulators stay), each pass stages the next one's patch -- (same block, slab 1), then (next
 // block, slab 0) -- inside its MFMA stream exactly as above; 2 fragment reads per up to 9 MFMAs; the epilogue rides in slab 1's last column.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#define DR2_LDS (2 * (DR_PATCHB + 1024))     // two patch buffers, each with the sink of the elements that do not exist behind it
+// two patch buffers, each with the sink of the elements that do not exist behind it (DR_SINK_END = 1144 bytes, rounded up to keep the
+// second buffer at the first one's alignment mod 256: the bank pattern of the fragment reads)
+#define DR2_SINKB 1280
+#define DR2_BUF (DR_PATCHB + DR2_SINKB)
+#define DR2_LDS (2 * DR2_BUF)
 struct ConvDirectR2Args {
     const float *x; const f16x8 *w2; const float *bias; float *y;
     int B, H, W, gxb, gyb, nblk;
@@ -373,10 +350,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r2_kernel(ConvDirectR2A
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int gq = lane >> 4, l15 = lane & 15;
 
-    const float amax = fminf(fmaxf(__uint_as_float(*p.amax_in), 1e-30f), 1e30f);
-    int e_;
-    (void)frexpf(32752.0f / amax, &e_);
-    const float sx = ldexpf(1.0f, e_ - 1);
+    const float sx = scale_le_32752(__uint_as_float(*p.amax_in));
     const float inv = p.inv_sw / sx;
 
     // blocks to workgroup PAIRS by XCD (contiguous eighths); the launch has an even number of workgroups per XCD
@@ -423,7 +397,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r2_kernel(ConvDirectR2A
     // MFMAs per patch of the kernel above: the per-element source offsets live in registers (an add and a select per request instead of
     // ten instructions), the elements that do not exist go to a sink at the SAME offset behind either patch buffer (one add per
     // destination), the scale is two packed multiplies, the column test one bit-field extract, one add and one unsigned compare)
-    constexpr int R2_BUF = DR_PATCHB + 1024;                   // a patch buffer + its sink
+    static_assert(DR_SINK_END <= DR2_SINKB && DR2_BUF % 256 == 0, "a sink store leaves its sink, or the second buffer moves in the banks");
     int st_dst[DR_NEL], st_src[DR_NEL];
     unsigned st_pc = 0, st_pc2 = 0;
 #pragma unroll
@@ -439,7 +413,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r2_kernel(ConvDirectR2A
     const int img_bytes = p.H * p.W * 512;
     u32x4 stg[DR_NEL];
     auto patch_load = [&](const Blk &b, int slab, int i) {
-        const __amdgpu_buffer_rsrc_t rsX = dr_rsrc((const char *)p.x + (int64_t)b.img * img_bytes, img_bytes);
+        const __amdgpu_buffer_rsrc_t rsX = buf_rsrc((const char *)p.x + (int64_t)b.img * img_bytes, img_bytes, RSRC_LIM16);
         const int blk_off = ((b.by * 8 - 1) * p.W + (b.bx * 16 - 1)) * 512 + slab * 256;
         int off = st_src[i] + blk_off;
         asm volatile("" : "+v"(off));                          // (computed by every lane: one select, no branch)
@@ -452,7 +426,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r2_kernel(ConvDirectR2A
         f32x2 w23 = f32x2{__uint_as_float(stg[i].z), __uint_as_float(stg[i].w)} * f32x2{s, s};
         asm("" : "+v"(w01), "+v"(w23));                        // (used AS pairs: hipcc keeps the two v_pk_mul_f32)
         const __half2 h01 = __floats2half2_rn(w01[0], w01[1]), h23 = __floats2half2_rn(w23[0], w23[1]);
-        const float d0 = dr_sub_half<0>(w01[0], h01), d1 = dr_sub_half<1>(w01[1], h01), d2 = dr_sub_half<0>(w23[0], h23), d3 = dr_sub_half<1>(w23[1], h23);
+        const float d0 = sub_half<0>(w01[0], h01), d1 = sub_half<1>(w01[1], h01), d2 = sub_half<0>(w23[0], h23), d3 = sub_half<1>(w23[1], h23);
         const __half2 l01 = __floats2half2_rn(d0, d1), l23 = __floats2half2_rn(d2, d3);
         char *d = patch + st_dst[i];
         *(uint2 *)d = make_uint2(*(const unsigned *)&h01, *(const unsigned *)&h23);
@@ -475,7 +449,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r2_kernel(ConvDirectR2A
     const int Ho = POOL ? p.H >> 1 : p.H, Wo = POOL ? p.W >> 1 : p.W;
     Blk eb = {0, 0, 0};
     auto epi_rows = [&](int k) {                               // POOL: pooled row k (output rows 2 k, 2 k + 1); else output row k
-        const __amdgpu_buffer_rsrc_t rsY = dr_rsrc((const char *)(p.y + (int64_t)eb.img * Ho * Wo * 128), (int64_t)Ho * Wo * 512);
+        const __amdgpu_buffer_rsrc_t rsY = buf_rsrc((const char *)(p.y + (int64_t)eb.img * Ho * Wo * 128), (int64_t)Ho * Wo * 512, RSRC_LIM16);
         const int ox = eb.bx * 16 + l15;
         const int ch_off = (64 * half + 16 * wave + 4 * gq) * 4;
         float4 v;
@@ -483,8 +457,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r2_kernel(ConvDirectR2A
         int off;
         if (POOL) {
             const int py = eb.by * 4 + k;
-            v.x = dr_max_xor1(dr_max(acc[2 * k][0], acc[2 * k + 1][0])); v.y = dr_max_xor1(dr_max(acc[2 * k][1], acc[2 * k + 1][1]));
-            v.z = dr_max_xor1(dr_max(acc[2 * k][2], acc[2 * k + 1][2])); v.w = dr_max_xor1(dr_max(acc[2 * k][3], acc[2 * k + 1][3]));
+            v.x = max_f32_xor1(max_f32(acc[2 * k][0], acc[2 * k + 1][0])); v.y = max_f32_xor1(max_f32(acc[2 * k][1], acc[2 * k + 1][1]));
+            v.z = max_f32_xor1(max_f32(acc[2 * k][2], acc[2 * k + 1][2])); v.w = max_f32_xor1(max_f32(acc[2 * k][3], acc[2 * k + 1][3]));
             store = ((l15 & 1) == 0) & ((ox >> 1) < Wo) & (py < Ho);
             off = (py * Wo + (ox >> 1)) * 512 + ch_off;
         } else {
@@ -495,9 +469,9 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r2_kernel(ConvDirectR2A
         }
         v.x = v.x * inv + bv.x; v.y = v.y * inv + bv.y; v.z = v.z * inv + bv.z; v.w = v.w * inv + bv.w;
         if (RELU) { v.x = fmaxf(v.x, 0.0f); v.y = fmaxf(v.y, 0.0f); v.z = fmaxf(v.z, 0.0f); v.w = fmaxf(v.w, 0.0f); }
-        float m = dr_max(dr_max(fabsf(v.x), fabsf(v.y)), dr_max(fabsf(v.z), fabsf(v.w)));
+        float m = max_f32(max_f32(fabsf(v.x), fabsf(v.y)), max_f32(fabsf(v.z), fabsf(v.w)));
         asm volatile("" : "+v"(m), "+v"(off));
-        my_amax = dr_max(my_amax, store ? m : 0.0f);
+        my_amax = max_f32(my_amax, store ? m : 0.0f);
         u32x4 bits;
         bits.x = __float_as_uint(v.x); bits.y = __float_as_uint(v.y); bits.z = __float_as_uint(v.z); bits.w = __float_as_uint(v.w);
         if (!(DBG & 4)) __builtin_amdgcn_raw_buffer_store_b128(bits, rsY, store ? off : 0x7fffffff, 0, 0);
@@ -560,7 +534,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_direct_r2_kernel(ConvDirectR2A
 #pragma unroll
     for (int i = 0; i < DR_NEL; ++i) patch_split(cb, i, dr_smem);
     __syncthreads();
-    char *const buf0 = dr_smem, *const buf1 = dr_smem + R2_BUF;
+    char *const buf0 = dr_smem, *const buf1 = dr_smem + DR2_BUF;
     for (int bi = 0; bi < n_mine; ++bi) {
         const Blk nb = decode_blk(bi + 1);
         eb = cb;

@@ -31,6 +31,7 @@
 // per CU.  Epilogue: rescale, bias, shortcut (either format), ReLU, store (either format) in 128-byte runs through per-tile buffer
 // descriptors (no branch: rows beyond the last pixel are out of range), max |y| into the slot the next layer reads.
 #include "common.h"
+#include "pairs.h"
 #include <type_traits>
 #include <hip/hip_fp16.h>
 
@@ -54,52 +55,21 @@ struct ConvIgemmArgs {
     int pool;              // stem only: MaxPool2d(3, 2, 1) of the ReLU output fused (8 x 16-pixel tiles, y = the POOLED map, zeroed by the host)
     const unsigned *amax_in; float inv_sw; unsigned *amax_out;
     // pair-format activations (AM = 2 reads them, out_pairs writes them): [pixel][channel block of 32][hi 32 | lo 32] halfs of s x, s the
-    // power of two ci_scale() derives from the 4-byte BOUND slot that travels with the tensor
+    // power of two scale_in_2p13_2p14 (pairs.h) derives from the 4-byte BOUND slot that travels with the tensor
     const unsigned *xbound;            // AM = 2: the bound x's pairs were scaled by
-    int out_pairs;                     // y leaves as pairs scaled by ci_scale(bound_out)
+    int out_pairs;                     // y leaves as pairs scaled by scale_in_2p13_2p14(bound_out)
     float wl1, bmax;                   // max over output channels of sum |w|, max |bias|: bound_out = max|x| wl1 + bmax (+ max|res|)
     unsigned *bound_out;               // receives that bound (written by workgroup (0, 0))
-    int res_pairs;                     // res is in pair format, scaled by ci_scale(*res_bound)
+    int res_pairs;                     // res is in pair format, scaled by scale_in_2p13_2p14(*res_bound)
     const unsigned *res_bound;         // bound slot of res (pairs) / a bound of max |res| (float32 res, when out_pairs)
     int dbg;                           // measurement build (-DCSLAM_ABLATIONS, CSLAM_CI_DBG; WRONG results, timing) of the AM = 2 loop: 1 no
                                        // activation requests after the prologue, 2 no weight requests, 4 no barrier, 8 no wait for the
                                        // requests, 16 no products, 32 no fragment reads either, 64 no epilogue, 128 activation requests for the taps with kw = 0 only
 };
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t ci_rsrc(const char *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a);
-    const int n = __builtin_amdgcn_readfirstlane((int)(bytes > 0x7fffffff ? 0x7fffffff : bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)u, 0, n, 0x00020000);
-}
 __device__ __forceinline__ cf4 ci_bload16(__amdgpu_buffer_rsrc_t rs, int voff, int soff) {
     const cu4 v = __builtin_amdgcn_raw_buffer_load_b128(rs, voff, soff, 0);
     return (cf4){__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
-}
-// (a __device__ function, not the builtin inside the kernel's lambda: with the LDS-DMA builtin called from a lambda hipcc 7.2's HOST
-// pass emits no launch stub for the kernel and says nothing -- the library then fails to load with an undefined symbol)
-__device__ __forceinline__ void ci_blds16(__amdgpu_buffer_rsrc_t rs, int voff, int soff, char *lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)lds_wave_base, 16, voff, soff, 0, 0);
-}
-// the power of two that brings max |x| into [2^13, 2^14): the hi halves keep 11 bits, the lo halves stay normal fp16 numbers for
-// every value within 2^-10 of the maximum (smaller ones lose nothing that matters: their absolute error is 2^-25 of the scaled maximum)
-__device__ __forceinline__ float ci_scale(unsigned amax_bits) {
-    const float a = fminf(fmaxf(__uint_as_float(amax_bits), 1e-30f), 1e30f);
-    int e;
-    (void)frexpf(a, &e);
-    return ldexpf(1.0f, 14 - e);
-}
-template <int HI>
-__host__ __device__ __forceinline__ float ci_sub_half(float v, __half2 h) {       // v - (float)half HI of h: one v_fma_mix_f32
-#if defined(__HIP_DEVICE_COMPILE__)
-    float d;
-    const unsigned hb = *(const unsigned *)&h;
-    if (HI) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    return d;
-#else
-    return v - (HI ? __high2float(h) : __low2float(h));
-#endif
 }
 
 // AM: how the activation tile reaches LDS.  0: float32 NHWC, split while it is staged; 1: the 3-channel stem (float32); 2: pair-format
@@ -173,12 +143,12 @@ __global__ __launch_bounds__(256, (KWS && TM == 256) ? 1 : 2) void conv_igemm_h2
         hi0 = ho * p.stride - p.pad;
         wi0 = wo * p.stride - p.pad;
     }
-    const float sc = ci_scale(PAIRS ? *p.xbound : *p.amax_in);
+    const float sc = scale_in_2p13_2p14(__uint_as_float(PAIRS ? *p.xbound : *p.amax_in));
     // descriptor from the image of the workgroup's first pixel on (the host checks that a tile's span of images stays below 2^31 bytes)
     const int b0 = __builtin_amdgcn_readfirstlane(tile2d ? tb : (int)(((int64_t)mt * TM) / (p.Ho * p.Wo)));
     const int64_t img = (int64_t)p.H * p.W * p.Cin;
     const int64_t xbytes = (int64_t)(p.B - b0) * img * 4;
-    const __amdgpu_buffer_rsrc_t rsX = ci_rsrc((const char *)(p.x + b0 * img), STEM && xbytes > CI_OOB - 1 ? CI_OOB - 1 : xbytes);
+    const __amdgpu_buffer_rsrc_t rsX = buf_rsrc((const char *)(p.x + b0 * img), STEM && xbytes > CI_OOB - 1 ? CI_OOB - 1 : xbytes, RSRC_LIM);
     const int pixoff0 = ((b_ - b0) * p.H + hi0) * p.W + wi0;
     int coloff[STEM ? 16 : 1];
     if (STEM) {
@@ -227,8 +197,8 @@ __global__ __launch_bounds__(256, (KWS && TM == 256) ? 1 : 2) void conv_igemm_h2
         for (int q = 0; q < 4; ++q) {
             const cf4 v = areg[q] * sc;
             const __half2 h0 = __floats2half2_rn(v.x, v.y), h1 = __floats2half2_rn(v.z, v.w);
-            const __half2 l0 = __floats2half2_rn(ci_sub_half<0>(v.x, h0), ci_sub_half<1>(v.y, h0));
-            const __half2 l1 = __floats2half2_rn(ci_sub_half<0>(v.z, h1), ci_sub_half<1>(v.w, h1));
+            const __half2 l0 = __floats2half2_rn(sub_half<0>(v.x, h0), sub_half<1>(v.y, h0));
+            const __half2 l1 = __floats2half2_rn(sub_half<0>(v.z, h1), sub_half<1>(v.w, h1));
             hh[2 * q] = *(const unsigned *)&h0; hh[2 * q + 1] = *(const unsigned *)&h1;
             ll[2 * q] = *(const unsigned *)&l0; ll[2 * q + 1] = *(const unsigned *)&l1;
         }
@@ -263,7 +233,7 @@ __global__ __launch_bounds__(256, (KWS && TM == 256) ? 1 : 2) void conv_igemm_h2
             // (unsigned compares: one per coordinate; the tap's offset is wave-uniform; select, not branch)
             const bool in = (unsigned)(pa_h[i] + kh) < (unsigned)p.H && (unsigned)(pa_w[i] + kw) < (unsigned)p.W;
             const int off = pa_off[i] + tapoff;
-            ci_blds16(rsX, in ? off : 0x7fffffff, cb * 128, smem + st * STAGE + i * (256 * 16) + wave * 1024);
+            buf_lds16(rsX, in ? off : 0x7fffffff, cb * 128, smem + st * STAGE + i * (256 * 16) + wave * 1024);
         }
     };
 
@@ -289,7 +259,7 @@ __global__ __launch_bounds__(256, (KWS && TM == 256) ? 1 : 2) void conv_igemm_h2
         for (int i = 0; i < (KWS ? KA_NP : 0); ++i) {
             if (i < i0 || i >= i1 || (i == KA_NP - 1 && wave != 0)) continue;      // (the last piece = rows TM .. TM + 7: one wave's 1 KB; the buffer ends there)
             const bool in = (unsigned)(ka_h[i] + kh) < (unsigned)p.H;
-            ci_blds16(rsX, in ? ka_off[i] + rowoff : 0x7fffffff, cb * 128, smem + abuf * KA_BYTES + i * (256 * 16) + wave * 1024);
+            buf_lds16(rsX, in ? ka_off[i] + rowoff : 0x7fffffff, cb * 128, smem + abuf * KA_BYTES + i * (256 * 16) + wave * 1024);
         }
     };
 
@@ -326,8 +296,8 @@ __global__ __launch_bounds__(256, (KWS && TM == 256) ? 1 : 2) void conv_igemm_h2
             for (int q = 0; q < 4; ++q) {
                 const cf4 v = kr[it][q] * sc;
                 const __half2 h0 = __floats2half2_rn(v.x, v.y), h1 = __floats2half2_rn(v.z, v.w);
-                const __half2 l0 = __floats2half2_rn(ci_sub_half<0>(v.x, h0), ci_sub_half<1>(v.y, h0));
-                const __half2 l1 = __floats2half2_rn(ci_sub_half<0>(v.z, h1), ci_sub_half<1>(v.w, h1));
+                const __half2 l0 = __floats2half2_rn(sub_half<0>(v.x, h0), sub_half<1>(v.y, h0));
+                const __half2 l1 = __floats2half2_rn(sub_half<0>(v.z, h1), sub_half<1>(v.w, h1));
                 hh[2 * q] = *(const unsigned *)&h0; hh[2 * q + 1] = *(const unsigned *)&h1;
                 ll[2 * q] = *(const unsigned *)&l0; ll[2 * q + 1] = *(const unsigned *)&l1;
             }
@@ -340,7 +310,7 @@ __global__ __launch_bounds__(256, (KWS && TM == 256) ? 1 : 2) void conv_igemm_h2
 
     // ---- weight tile by LDS-DMA: chunk pch = i * 256 + tid -> row pch >> 3, physical slot pch & 7 = logical chunk slot ^ swz(row)
     const int pitchw = p.nk * CI_ROWB;
-    const __amdgpu_buffer_rsrc_t rsB = ci_rsrc(p.w2 + (int64_t)nt * TN * pitchw, (int64_t)TN * pitchw);
+    const __amdgpu_buffer_rsrc_t rsB = buf_rsrc(p.w2 + (int64_t)nt * TN * pitchw, (int64_t)TN * pitchw, RSRC_LIM);
     int voffB[NLB];
 #pragma unroll
     for (int i = 0; i < NLB; ++i) {
@@ -355,7 +325,7 @@ __global__ __launch_bounds__(256, (KWS && TM == 256) ? 1 : 2) void conv_igemm_h2
         if ((PAIRS || KWS) && ++bw_tap == ntap) { bw_tap = 0; ++bw_cb; }
 #pragma unroll
         for (int i = 0; i < NLB; ++i)
-            ci_blds16(rsB, voffB[i], widx * CI_ROWB, smem + (KWS ? 2 * KA_BYTES + st * OPB : st * STAGE + OPA) + i * (256 * 16) + wave * 1024);
+            buf_lds16(rsB, voffB[i], widx * CI_ROWB, smem + (KWS ? 2 * KA_BYTES + st * OPB : st * STAGE + OPA) + i * (256 * 16) + wave * 1024);
     };
 
     // ---- fragments: row * 128 + (chunk ^ swz) * 16, chunk = 4 lo + 2 s + h for the 16-channel K step s
@@ -678,10 +648,10 @@ __global__ __launch_bounds__(256, (KWS && TM == 256) ? 1 : 2) void conv_igemm_h2
             const float xmax = __uint_as_float(*p.amax_in);
             const float rmax = p.res ? __uint_as_float(*p.res_bound) : 0.0f;
             const float bound = (xmax * p.wl1 + p.bmax + rmax) * 1.001f;          // >= max |y| whatever the rounding of the products
-            s_out = ci_scale(__float_as_uint(bound));
+            s_out = scale_in_2p13_2p14(bound);
             if (mt == 0 && nt == 0 && tid == 0) *p.bound_out = __float_as_uint(bound);
         }
-        if (p.res && p.res_pairs) inv_sres = 1.0f / ci_scale(*p.res_bound);
+        if (p.res && p.res_pairs) inv_sres = 1.0f / scale_in_2p13_2p14(__uint_as_float(*p.res_bound));
         // Stores and shortcut loads go through buffer descriptors that begin at the tile's first pixel and end with the tensor: a row
         // beyond the last pixel is out of range -- the load returns zero, the store is dropped -- so the epilogue has no branch (with
         // `if (pixel < P)` around every access the compiler serialised 64 load -> wait -> store sequences per lane: 0.7 ms of layer1's
@@ -689,8 +659,8 @@ __global__ __launch_bounds__(256, (KWS && TM == 256) ? 1 : 2) void conv_igemm_h2
         const int64_t tile0 = (int64_t)mt * TM * p.Cout;                       // the tile's first value (both formats: 4 bytes per value)
         const int64_t rows_left = (int64_t)p.P - (int64_t)mt * TM;
         const int64_t tile_bytes = (rows_left < TM ? rows_left : TM) * p.Cout * 4;
-        const __amdgpu_buffer_rsrc_t rsY = ci_rsrc((const char *)(p.y + tile0), tile_bytes);
-        const __amdgpu_buffer_rsrc_t rsR = ci_rsrc((const char *)((p.res ? p.res : p.y) + tile0), tile_bytes);
+        const __amdgpu_buffer_rsrc_t rsY = buf_rsrc((const char *)(p.y + tile0), tile_bytes, RSRC_LIM);
+        const __amdgpu_buffer_rsrc_t rsR = buf_rsrc((const char *)((p.res ? p.res : p.y) + tile0), tile_bytes, RSRC_LIM);
         const float floor_ = p.relu ? 0.0f : -INFINITY;
         // (the operand formats as compile-time constants of six copies of the loop: as runtime flags they left a branch per element)
         auto epilogue = [&](auto res_c, auto outp_c) {
@@ -813,7 +783,7 @@ __global__ __launch_bounds__(512, 1) void conv_stem_pool_patch_kernel(StemPatchA
     char *s_w = smem;                                  // [kh 7][s 2][n 2][hi | lo][lane 64] x 16 bytes
     char *s_patch = smem + SP_WBYTES + grp * SP_GROUP; // [buffer 2][hi | lo] planes of this group
     float *T = (float *)(s_patch + 4 * SP_PLANE);
-    const float sc = ci_scale(*p.amax_in);
+    const float sc = scale_in_2p13_2p14(__uint_as_float(*p.amax_in));
     const float inv = p.inv_sw / sc;
     // ---- weights: global rows [co][kh][hi 32 | lo 32] -> fragment order
     for (int e = tid; e < 7 * 2 * 2 * 2 * 64; e += 512) {
@@ -833,7 +803,7 @@ __global__ __launch_bounds__(512, 1) void conv_stem_pool_patch_kernel(StemPatchA
     // SQ_LDS_BANK_CONFLICT was 22 % of the kernel's LDS cycles)
     auto patch_request = [&](int tile) {               // 21 rows x 112 floats of the tile's patch -> registers (zeros outside the image)
         const int tb = tile / p.tpi, t = tile - tb * p.tpi, tr = t / p.tcols, tc = t - tr * p.tcols;
-        const __amdgpu_buffer_rsrc_t rs = ci_rsrc((const char *)(p.x + tb * img), img * 4);
+        const __amdgpu_buffer_rsrc_t rs = buf_rsrc((const char *)(p.x + tb * img), img * 4, RSRC_LIM);
         const int gy0 = tr * 16 - 3, gx0 = (tc * 32 - 3) * 3;
 #pragma unroll
         for (int j = 0; j < 5; ++j) {

@@ -32,6 +32,7 @@
 #include <type_traits>
 #include <hip/hip_fp16.h>
 #include "common.h"
+#include "pairs.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -71,40 +72,6 @@ extern "C" __attribute__((visibility("default"))) int cslam_debug_sd_prof_dev(vo
 #define SD_PROF 0
 #endif
 
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t sd_rsrc(const char *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a);
-    const int n = __builtin_amdgcn_readfirstlane((int)(bytes > 0x7ffffff0 ? 0x7ffffff0 : bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)u, 0, n, 0x00020000);
-}
-__device__ __forceinline__ unsigned sd_pack(float v) {                    // [fp16(v) | fp16(v - fp16(v)) << 16]
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    return (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
-}
-// v - (float)half HI of the packed pair h: one v_fma_mix_f32 (the fp16 operand is read straight out of the packed register; written as
-// fmaf((float)half, -1, v) hipcc 7.2 converts the half back to float and subtracts: three instructions per value)
-template <int HI>
-__device__ __forceinline__ float sd_sub_half(float v, __half2 h) {
-    float d;
-    const unsigned hb = *(const unsigned *)&h;
-    if (HI) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    return d;
-}
-__device__ __forceinline__ float sd_max(float a, float b) {   // (fmaxf first canonicalises both operands: two more instructions per maximum)
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
-    return r;
-}
-// max(v, v of lane ^ 1): a DPP quad permutation (as `__shfl_xor` it is a ds_bpermute_b32 with an LDS round trip behind it)
-__device__ __forceinline__ float sd_max_xor1(float v) {
-    const float a = __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));   // quad_perm [1, 0, 3, 2]
-    float r;
-    asm("v_max_f32 %0, %1, %2" : "=v"(r) : "v"(v), "v"(a));   // (fmaxf would first canonicalise both operands: two more instructions per maximum)
-    return r;
-}
-
 // DBG (builds with -DCSLAM_ABLATIONS only; WRONG results, timing): 1 = no first layer inside the loop, 2 = no fragment reads after a block's
 // first two, 4 = no epilogue stores, 8 = first layer without its image reads, 16 = ... without its patch stores
 template <bool POOL, int DBG = 0>
@@ -125,6 +92,7 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
     const float inv1 = p.inv_sw1 / s1;
     float bound = 0.0f;
     for (int c = 0; c < 64; ++c) bound = fmaxf(bound, fabsf(p.b1 ? p.b1[c] : 0.0f) + a0 * p.sumw[c]);
+    // rule B of pairs.h (scale_le_32752) written out: with the helper, hipcc 7.2 allocates this kernel's scalar registers differently
     bound = fminf(fmaxf(bound, 1e-30f), 1e30f);
     (void)frexpf(32752.0f / bound, &e_);
     const float sx = ldexpf(1.0f, e_ - 1);
@@ -202,7 +170,7 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
 #pragma unroll
         for (int j = 0; j < 3; ++j)
             if (e_dst[j] >= 0) {
-                const unsigned v = sd_pack(raw[j] * s1);
+                const unsigned v = pack_pair(raw[j] * s1);
                 s_img[e_dst[j]] = v;
                 if ((e_rc[j] >> 16) == 2) s_img[SD_IMG + (e_rc[j] & 255) * 17 + ((e_rc[j] >> 8) & 255)] = v;
             }
@@ -266,8 +234,8 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
             return;
         }
         const __half2 h01 = __floats2half2_rn(c1v[i][0], c1v[i][1]), h23 = __floats2half2_rn(c1v[i][2], c1v[i][3]);
-        const float d0 = sd_sub_half<0>(c1v[i][0], h01), d1 = sd_sub_half<1>(c1v[i][1], h01);
-        const float d2 = sd_sub_half<0>(c1v[i][2], h23), d3 = sd_sub_half<1>(c1v[i][3], h23);
+        const float d0 = sub_half<0>(c1v[i][0], h01), d1 = sub_half<1>(c1v[i][1], h01);
+        const float d2 = sub_half<0>(c1v[i][2], h23), d3 = sub_half<1>(c1v[i][3], h23);
         const __half2 l01 = __floats2half2_rn(d0, d1), l23 = __floats2half2_rn(d2, d3);
         if ((DBG & 16) == 0 && (2 * g + i < 11 || l15 < 4)) {  // (g is a constant where this is called: tile 11 alone has pixels that do not exist)
             char *d = patch + c1_dst[2 * g + i];
@@ -307,7 +275,7 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
     Blk ecb = {0, 0, 0};
     bool e_ok = false;
     auto epi_piece = [&](int k) {
-        const __amdgpu_buffer_rsrc_t rsY = sd_rsrc((const char *)(p.y + (int64_t)ecb.img * Ho * Wo * 64), (int64_t)Ho * Wo * 256);
+        const __amdgpu_buffer_rsrc_t rsY = buf_rsrc((const char *)(p.y + (int64_t)ecb.img * Ho * Wo * 64), (int64_t)Ho * Wo * 256, RSRC_LIM16);
         const int ox = ecb.bx * 16 + l15;
         const int ch_off = (16 * wave + 4 * gq) * 4;
         if (POOL) {
@@ -315,15 +283,15 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
             float4 v;
             // 2 x 2 maximum first (the two rows sit in one lane, the two columns in lanes l, l ^ 1), then the exact rescale, bias and ReLU
             // on the survivor: all monotone
-            v.x = sd_max_xor1(sd_max(eacc[2 * k][0], eacc[2 * k + 1][0])); v.y = sd_max_xor1(sd_max(eacc[2 * k][1], eacc[2 * k + 1][1]));
-            v.z = sd_max_xor1(sd_max(eacc[2 * k][2], eacc[2 * k + 1][2])); v.w = sd_max_xor1(sd_max(eacc[2 * k][3], eacc[2 * k + 1][3]));
+            v.x = max_f32_xor1(max_f32(eacc[2 * k][0], eacc[2 * k + 1][0])); v.y = max_f32_xor1(max_f32(eacc[2 * k][1], eacc[2 * k + 1][1]));
+            v.z = max_f32_xor1(max_f32(eacc[2 * k][2], eacc[2 * k + 1][2])); v.w = max_f32_xor1(max_f32(eacc[2 * k][3], eacc[2 * k + 1][3]));
             v.x = fmaxf(v.x * inv2 + bv2.x, 0.0f); v.y = fmaxf(v.y * inv2 + bv2.y, 0.0f);
             v.z = fmaxf(v.z * inv2 + bv2.z, 0.0f); v.w = fmaxf(v.w * inv2 + bv2.w, 0.0f);
             const bool store = e_ok & ((l15 & 1) == 0) & ((ox >> 1) < Wo) & (py < Ho);          // (bitwise: `&&` became branches on exec)
-            float m = sd_max(sd_max(v.x, v.y), sd_max(v.z, v.w));
+            float m = max_f32(max_f32(v.x, v.y), max_f32(v.z, v.w));
             int off = (py * Wo + (ox >> 1)) * 256 + ch_off;
             asm volatile("" : "+v"(m), "+v"(off));             // computed by every lane: inside a select hipcc turns them into a branch, and a branch ends the region
-            my_amax = sd_max(my_amax, store ? m : 0.0f);
+            my_amax = max_f32(my_amax, store ? m : 0.0f);
             u32x4 bits;
             bits.x = __float_as_uint(v.x); bits.y = __float_as_uint(v.y); bits.z = __float_as_uint(v.z); bits.w = __float_as_uint(v.w);
             if (!(DBG & 4)) __builtin_amdgcn_raw_buffer_store_b128(bits, rsY, store ? off : 0x7fffffff, 0, 0);
@@ -335,10 +303,10 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
                 v.x = fmaxf(eacc[r][0] * inv2 + bv2.x, 0.0f); v.y = fmaxf(eacc[r][1] * inv2 + bv2.y, 0.0f);
                 v.z = fmaxf(eacc[r][2] * inv2 + bv2.z, 0.0f); v.w = fmaxf(eacc[r][3] * inv2 + bv2.w, 0.0f);
                 const bool store = e_ok & (ox < p.W) & (oy < p.H);
-                float m = sd_max(sd_max(v.x, v.y), sd_max(v.z, v.w));
+                float m = max_f32(max_f32(v.x, v.y), max_f32(v.z, v.w));
                 int off = (oy * p.W + ox) * 256 + ch_off;
                 asm volatile("" : "+v"(m), "+v"(off));
-                my_amax = sd_max(my_amax, store ? m : 0.0f);
+                my_amax = max_f32(my_amax, store ? m : 0.0f);
                 u32x4 bits;
                 bits.x = __float_as_uint(v.x); bits.y = __float_as_uint(v.y); bits.z = __float_as_uint(v.z); bits.w = __float_as_uint(v.w);
                 __builtin_amdgcn_raw_buffer_store_b128(bits, rsY, store ? off : 0x7fffffff, 0, 0);

@@ -110,7 +110,7 @@ __global__ __launch_bounds__(T_ * 64 / (16 * NTW), NTW == 4 ? 1 : 2) void sim_to
         }
         const int wave_chunk = wave * 1024;
         // the query copy is padded to whole tiles
-        const __amdgpu_buffer_rsrc_t rsB = pk_rsrc(p.q2 + (int64_t)(DBG == 2 ? 0 : qt) * T_ * p.ldq2, (int64_t)T_ * p.ldq2);
+        const __amdgpu_buffer_rsrc_t rsB = buf_rsrc(p.q2 + (int64_t)(DBG == 2 ? 0 : qt) * T_ * p.ldq2, (int64_t)T_ * p.ldq2, RSRC_LIM);
         // the bank tile the loader points at: a buffer resource over its rows (rows beyond the bank read as zero; the epilogue
         // masks them), rebuilt when the loader moves to another tile (once per nkt stages, on the scalar unit)
         __amdgpu_buffer_rsrc_t rsA;
@@ -118,13 +118,13 @@ __global__ __launch_bounds__(T_ * 64 / (16 * NTW), NTW == 4 ? 1 : 2) void sim_to
             const int t0 = DBG == 2 ? 0 : tile;
             int64_t rows = (int64_t)p.n_rows - (int64_t)t0 * T_;
             if (rows > T_) rows = T_;
-            rsA = pk_rsrc(p.bank2 + (int64_t)t0 * T_ * p.ldb2, rows * p.ldb2);
+            rsA = buf_rsrc(p.bank2 + (int64_t)t0 * T_ * p.ldb2, rows * p.ldb2, RSRC_LIM);
         };
         auto stage_load_part = [&](int stage, int kt, int i) {
             char *sA = smem + stage * STAGE;
             char *sB = sA + OPB;
-            pk_blds16(rsA, voffA[i], kt * PK_ROWB, sA + i * (NTHR * 16) + wave_chunk);
-            pk_blds16(rsB, voffB[i], kt * PK_ROWB, sB + i * (NTHR * 16) + wave_chunk);
+            buf_lds16(rsA, voffA[i], kt * PK_ROWB, sA + i * (NTHR * 16) + wave_chunk);
+            buf_lds16(rsB, voffB[i], kt * PK_ROWB, sB + i * (NTHR * 16) + wave_chunk);
         };
 
         // fragment read offsets: row * 128 + (chunk ^ swz) * 16, chunk = 4 lo + 2 s + h for K step s (16 channels) of the stage

@@ -1,35 +1,16 @@
 // sim_topk_pair_dev.h -- device helpers shared by the candidate-stage kernels on the fp16 matrix pipe (sim_topk_pair.hip: one
-// workgroup per (query tile, bank segment); sim_topk_ring.hip: persistent workgroups on a static, XCD-aligned schedule): the MUBUF
-// LDS-DMA request, the lane-local candidate update of a finished tile, the block merge of the lane lists.
+// workgroup per (query tile, bank segment); sim_topk_ring.hip: persistent workgroups on a static, XCD-aligned schedule): the
+// lane-local candidate update of a finished tile, the block merge of the lane lists (the LDS-DMA request: pairs.h).
 #pragma once
 #include <hip/hip_fp16.h>
 #include "bank.h"
 #include "sim_topk.h"
+#include "pairs.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
 #define PK_ROWB 128     // bytes of one 32-channel block of one row
-
-// LDS-DMA in the MUBUF encoding (`buffer_load_dwordx4 ... lds`), round 4.  `global_load_lds` is FLAT-encoded with an LDS operand:
-// hipcc's waitcnt pass marks it "pending flat" and from then on turns every `lgkmcnt(N)` into `lgkmcnt(0)` -- a K step's MFMAs then
-// wait for ALL fragment reads issued before them.  The buffer form carries no such mark (LDS reads are counted again), takes the
-// stage's K offset in an SGPR and the lane's row offset in ONE register (a 64-bit address per request before), and clamps in
-// hardware: rows beyond `num_records` read as zero.
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t pk_rsrc(const char *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a);
-    const int n = __builtin_amdgcn_readfirstlane((int)(bytes > 0x7fffffff ? 0x7fffffff : bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)u, 0, n, 0x00020000);
-}
-__device__ __forceinline__ void pk_blds16(__amdgpu_buffer_rsrc_t rs, int voff, int soff, char *lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)lds_wave_base, 16, voff, soff, 0, 0);
-}
-// the same request with cache-policy bits (gfx940+: aux bit 0 = sc0, bit 1 = nt, bit 4 = sc1); measurement build of sim_topk_ring.hip
-template <int AUX>
-__device__ __forceinline__ void pk_blds16_aux(__amdgpu_buffer_rsrc_t rs, int voff, int soff, char *lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)lds_wave_base, 16, voff, soff, 0, AUX);
-}
 
 
 // ---- tile epilogue: lane-local candidate update from the finished 32 MT x 64 wave tile, then clear the accumulators

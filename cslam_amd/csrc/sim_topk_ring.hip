@@ -126,13 +126,13 @@ __global__ __launch_bounds__(512, 2) void sim_topk_ring_kernel(RingArgs p) {
         int pv = 0x7fffffff;                             // wave 0: progress of patch slot `lane`, as last read
 
         if (ntiles > 0) {
-            const __amdgpu_buffer_rsrc_t rsB = pk_rsrc(p.q2 + (int64_t)((DBG & 2) ? 0 : qt) * T_ * p.ldq2, (int64_t)T_ * p.ldq2);
+            const __amdgpu_buffer_rsrc_t rsB = buf_rsrc(p.q2 + (int64_t)((DBG & 2) ? 0 : qt) * T_ * p.ldq2, (int64_t)T_ * p.ldq2, RSRC_LIM);
             __amdgpu_buffer_rsrc_t rsA;
             auto point_at_tile = [&](int r0) {               // the 256 bank rows from r0 on; rows at or beyond the task's end read as zero
                 const int t0 = (DBG & 2) ? 0 : r0;
                 int64_t rows = (int64_t)tk.row_end - (int64_t)r0;
                 if (rows > T_) rows = T_;
-                rsA = pk_rsrc(p.bank2 + (int64_t)t0 * p.ldb2, rows * p.ldb2);
+                rsA = buf_rsrc(p.bank2 + (int64_t)t0 * p.ldb2, rows * p.ldb2, RSRC_LIM);
             };
             auto stage_load_part = [&](int stage, int kt, int i) {
                 char *sA = smem + stage * STAGE;
@@ -140,8 +140,8 @@ __global__ __launch_bounds__(512, 2) void sim_topk_ring_kernel(RingArgs p) {
                 // DBG bits 6-8 / 9-11 (measurement build): cache policy of the bank / query requests (1 = sc0, 2 = nt, 4 = sc1)
                 constexpr int PA = (DBG >> 6) & 7, PB = (DBG >> 9) & 7;
                 constexpr int AUXA = (PA & 3) | ((PA & 4) << 2), AUXB = (PB & 3) | ((PB & 4) << 2);
-                pk_blds16_aux<AUXA>(rsA, voffA0 + i * stepA, kt * PK_ROWB, sA + i * (NTHR * 16) + wave_chunk);
-                pk_blds16_aux<AUXB>(rsB, voffB0, kt * PK_ROWB + i * stepB, sB + i * (NTHR * 16) + wave_chunk);
+                buf_lds16<AUXA>(rsA, voffA0 + i * stepA, kt * PK_ROWB, sA + i * (NTHR * 16) + wave_chunk);
+                buf_lds16<AUXB>(rsB, voffB0, kt * PK_ROWB + i * stepB, sB + i * (NTHR * 16) + wave_chunk);
             };
 
             f32x16 acc[MT][NTW];
@@ -265,7 +265,7 @@ __global__ __launch_bounds__(512, 2) void sim_topk_ring_kernel(RingArgs p) {
                     // (nobody reads them before the tile's epilogue, 63 stage barriers from here; the previous tile's were read in
                     // front of this stage); rows beyond the bank read as zero and are masked by the row limits
                     if (wave < 4) {
-                        const __amdgpu_buffer_rsrc_t rsI = pk_rsrc((const char *)p.invs, (int64_t)p.n_rows * 4);
+                        const __amdgpu_buffer_rsrc_t rsI = buf_rsrc((const char *)p.invs, (int64_t)p.n_rows * 4, RSRC_LIM);
                         __builtin_amdgcn_raw_ptr_buffer_load_lds(rsI, (__attribute__((address_space(3))) void *)((char *)s_inv + (tpar * 4 + wave) * 256), 4,
                                                                  (tile + tid) * 4, 0, 0, 0);
                     }
@@ -350,12 +350,12 @@ __global__ __launch_bounds__(512, 2) void sim_topk_ring_kernel(RingArgs p) {
                 auto load = [&](int slot, int kt) {
                     char *sA = smem + slot * SLOT, *sB = sA + OPB / 2;
 #pragma unroll
-                    for (int i = 0; i < NLD / 2; ++i) pk_blds16(rsA, voffA0 + i * stepA, kt * PK_ROWB, sA + i * (NTHR * 16) + wave_chunk);
+                    for (int i = 0; i < NLD / 2; ++i) buf_lds16(rsA, voffA0 + i * stepA, kt * PK_ROWB, sA + i * (NTHR * 16) + wave_chunk);
 #pragma unroll
-                    for (int i = 0; i < NLD; ++i) pk_blds16(rsB, voffB0, kt * PK_ROWB + i * stepB, sB + i * (NTHR * 16) + wave_chunk);
+                    for (int i = 0; i < NLD; ++i) buf_lds16(rsB, voffB0, kt * PK_ROWB + i * stepB, sB + i * (NTHR * 16) + wave_chunk);
                 };
                 if (wave < 4) {
-                    const __amdgpu_buffer_rsrc_t rsI = pk_rsrc((const char *)p.invs, (int64_t)p.n_rows * 4);
+                    const __amdgpu_buffer_rsrc_t rsI = buf_rsrc((const char *)p.invs, (int64_t)p.n_rows * 4, RSRC_LIM);
                     __builtin_amdgcn_raw_ptr_buffer_load_lds(rsI, (__attribute__((address_space(3))) void *)((char *)s_inv + (tpar * 4 + wave) * 256), 4,
                                                              (tile + tid) * 4, 0, 0, 0);
                 }

@@ -26,6 +26,7 @@
 // 1 / (sV sU), bias, (shortcut), ReLU, 2x2 max, NHWC stores, max |y| for the next layer's scale.
 #include <stdlib.h>
 #include "common.h"
+#include "pairs.h"
 
 typedef float f4 __attribute__((ext_vector_type(4)));
 typedef unsigned u4 __attribute__((ext_vector_type(4)));
@@ -41,12 +42,6 @@ typedef _Float16 h8 __attribute__((ext_vector_type(8)));
 __device__ __forceinline__ void wh_glds16(const float *g, float *lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
                                      (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-__device__ __forceinline__ float wh_scale(unsigned amax_bits) {          // = wino_h3_scale (winograd.hip)
-    const float a = fminf(fmaxf(__uint_as_float(amax_bits), 1e-30f), 1e30f);
-    int e;
-    (void)frexpf(327.68f / a, &e);
-    return ldexpf(1.0f, e - 1);
 }
 __device__ __forceinline__ void wh_bt(float &d0, float &d1, float &d2, float &d3, float &d4, float &d5) {
     const float r0 = 4.0f * d0 - 5.0f * d2 + d4;
@@ -64,11 +59,6 @@ __device__ __forceinline__ void wh_at(float m0, float m1, float m2, float m3, fl
     s1 = b + 2.0f * e;
     s2 = a + 4.0f * c;
     s3 = b + 8.0f * e + m5;
-}
-__device__ __forceinline__ unsigned wh_pack(float v) {                    // [fp16(v) | fp16(v - fp16(v)) << 16]
-    const _Float16 hi = (_Float16)v;
-    const _Float16 lo = (_Float16)(v - (float)hi);
-    return (unsigned)__builtin_bit_cast(unsigned short, hi) | ((unsigned)__builtin_bit_cast(unsigned short, lo) << 16);
 }
 
 // DBG & 32 (CSLAM_WFH_PROF=1, results stay correct): waves 0 and 4 of workgroup 0 add up the shader cycles (s_memtime) they
@@ -125,9 +115,9 @@ __global__ __launch_bounds__(512, 2) void wino4_fused_c64_h_kernel(
         st_inv1 = st_inv_sw / st_s1;
         float bound = 0.0f;
         for (int c = 0; c < 64; ++c) bound = fmaxf(bound, fabsf(st_b1 ? st_b1[c] : 0.0f) + a0 * st_sumw[c]);
-        sc_ = wh_scale(__float_as_uint(bound));
+        sc_ = scale_le_327_68(bound);
     } else {
-        sc_ = wh_scale(*amax_in);
+        sc_ = scale_le_327_68(__uint_as_float(*amax_in));
     }
     const float sc = sc_;
     const float inv = inv_su / sc;
@@ -187,7 +177,7 @@ __global__ __launch_bounds__(512, 2) void wino4_fused_c64_h_kernel(
             if (e < ST_IMG) {
                 const int ci = (e >= ST_IPL) + (e >= 2 * ST_IPL);
                 const int rem = e - ci * ST_IPL;
-                s_img[3 * rem + ci] = wh_pack(s_raw[e] * st_s1);
+                s_img[3 * rem + ci] = pack_pair(s_raw[e] * st_s1);
             }
         }
     };
@@ -351,7 +341,7 @@ __global__ __launch_bounds__(512, 2) void wino4_fused_c64_h_kernel(
 #pragma unroll
                 for (int i = 0; i < 6; ++i)
 #pragma unroll
-                    for (int j = 0; j < 6; ++j) s_v[(6 * i + j) * NT * WH_VS + t_dst] = wh_pack(d[i][j]);
+                    for (int j = 0; j < 6; ++j) s_v[(6 * i + j) * NT * WH_VS + t_dst] = pack_pair(d[i][j]);
             }
             // V complete: LDS stores drained, then a RAW barrier -- __syncthreads() would also wait for the LDS-DMA of the
             // next patch (a pending LDS write), which is meant to stay in flight across this barrier

@@ -27,6 +27,7 @@
 // Bound: HBM for Cin <= 256 (V2 in + M out = 4 (Cin + Cout) bytes per tile row and frequency against 6 Cin Cout flop),
 // about balanced at 512 x 512.
 #include "common.h"
+#include "pairs.h"
 #include <type_traits>
 #include <hip/hip_fp16.h>
 
@@ -41,17 +42,6 @@ typedef unsigned wu2 __attribute__((ext_vector_type(2)));
 __device__ __forceinline__ void wg_glds16(const char *g, char *lds_wave_base) {
     __builtin_amdgcn_global_load_lds((const __attribute__((address_space(1))) void *)g,
                                      (__attribute__((address_space(3))) void *)lds_wave_base, 16, 0, 0);
-}
-// LDS-DMA in the MUBUF encoding (round 4; sim_topk_pair.hip has the why: hipcc counts LDS reads again, the K offset travels in an
-// SGPR, the lane's offset is one register, rows beyond `bytes` read as zero)
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t wg_rsrc(const char *base, int64_t bytes) {
-    const uint64_t a = (uint64_t)base;
-    const uint64_t u = ((uint64_t)(unsigned)__builtin_amdgcn_readfirstlane((int)(a >> 32)) << 32) | (unsigned)__builtin_amdgcn_readfirstlane((int)a);
-    const int n = __builtin_amdgcn_readfirstlane((int)(bytes > 0x7fffffff ? 0x7fffffff : bytes));
-    return __builtin_amdgcn_make_buffer_rsrc((void *)u, 0, n, 0x00020000);
-}
-__device__ __forceinline__ void wg_blds16(__amdgpu_buffer_rsrc_t rs, int voff, int soff, char *lds_wave_base) {
-    __builtin_amdgcn_raw_ptr_buffer_load_lds(rs, (__attribute__((address_space(3))) void *)lds_wave_base, 16, voff, soff, 0, 0);
 }
 
 struct WinoGemmArgs {
@@ -134,14 +124,14 @@ __global__ __launch_bounds__(512, 2) void wino_gemm_h2_kernel(WinoGemmArgs p) {
     auto point_at = [&](const Item &c) {
         int64_t rows = (int64_t)p.T - (int64_t)c.mt * TM;
         if (rows > TM) rows = TM;
-        rsA = wg_rsrc(p.V2 + ((int64_t)c.xi * p.T + (int64_t)c.mt * TM) * pitch, rows * pitch);
-        rsB = wg_rsrc(p.U2 + ((int64_t)c.xi * p.Cout + (int64_t)c.nt * TN) * pitch, (int64_t)TN * pitch);
+        rsA = buf_rsrc(p.V2 + ((int64_t)c.xi * p.T + (int64_t)c.mt * TM) * pitch, rows * pitch, RSRC_LIM);
+        rsB = buf_rsrc(p.U2 + ((int64_t)c.xi * p.Cout + (int64_t)c.nt * TN) * pitch, (int64_t)TN * pitch, RSRC_LIM);
     };
     auto load_part_a = [&](int stage, int kt, int i) {
-        wg_blds16(rsA, voffA[i], kt * WG_ROWB, smem + stage * STAGE + i * (512 * 16) + wave_chunk);
+        buf_lds16(rsA, voffA[i], kt * WG_ROWB, smem + stage * STAGE + i * (512 * 16) + wave_chunk);
     };
     auto load_part_b = [&](int stage, int kt, int i) {
-        wg_blds16(rsB, voffB[i], kt * WG_ROWB, smem + stage * STAGE + OPA + i * (512 * 16) + wave_chunk);
+        buf_lds16(rsB, voffB[i], kt * WG_ROWB, smem + stage * STAGE + OPA + i * (512 * 16) + wave_chunk);
     };
 
     // fragment read offsets: row * 128 + ((chunk) ^ swz) * 16, chunk = 4 * lo + 2 * s + h for K step s of the stage
@@ -347,12 +337,12 @@ __global__ __launch_bounds__(256, 1) void wino_gemm_h2_big_kernel(WinoGemmArgs p
     auto point_at = [&](const Item &c) {
         int64_t rows = (int64_t)p.T - (int64_t)c.mt * TM;
         if (rows > TM) rows = TM;
-        rsA = wg_rsrc(p.V2 + ((int64_t)c.xi * p.T + (int64_t)c.mt * TM) * pitch, rows * pitch);
-        rsB = wg_rsrc(p.U2 + ((int64_t)c.xi * p.Cout + (int64_t)c.nt * TN) * pitch, (int64_t)TN * pitch);
+        rsA = buf_rsrc(p.V2 + ((int64_t)c.xi * p.T + (int64_t)c.mt * TM) * pitch, rows * pitch, RSRC_LIM);
+        rsB = buf_rsrc(p.U2 + ((int64_t)c.xi * p.Cout + (int64_t)c.nt * TN) * pitch, (int64_t)TN * pitch, RSRC_LIM);
     };
     auto load_part = [&](int stage, int kt, int i) {          // parts 0..7: A, 8..15: B
-        if (i < NLA) wg_blds16(rsA, voff0 + i * step32, kt * WG_ROWB, smem + stage * STAGE + i * (256 * 16) + wave_chunk);
-        else wg_blds16(rsB, voff0, kt * WG_ROWB + (i - NLA) * step32, smem + stage * STAGE + OPA + (i - NLA) * (256 * 16) + wave_chunk);
+        if (i < NLA) buf_lds16(rsA, voff0 + i * step32, kt * WG_ROWB, smem + stage * STAGE + i * (256 * 16) + wave_chunk);
+        else buf_lds16(rsB, voff0, kt * WG_ROWB + (i - NLA) * step32, smem + stage * STAGE + OPA + (i - NLA) * (256 * 16) + wave_chunk);
     };
 
     // The per-lane address constants of the K loop (request offset, fragment offsets) are re-derived at the top of every item from
@@ -479,8 +469,8 @@ __global__ __launch_bounds__(256, 1) void wino_gemm_h2_big_kernel(WinoGemmArgs p
             int64_t rows = (int64_t)p.T - row0;
             if (rows < 0) rows = 0;
             const int col0 = c.nt * TN + wn * 128;
-            const __amdgpu_buffer_rsrc_t rsM = wg_rsrc((const char *)(p.M + ((int64_t)c.xi * p.T + row0) * p.Cout + col0),
-                                                       rows > 0 ? rows * p.Cout * 4 - (int64_t)col0 * 4 : 0);   // a wave tile beyond T: nothing is in range
+            const __amdgpu_buffer_rsrc_t rsM = buf_rsrc((const char *)(p.M + ((int64_t)c.xi * p.T + row0) * p.Cout + col0),
+                                                       rows > 0 ? rows * p.Cout * 4 - (int64_t)col0 * 4 : 0, RSRC_LIM);   // a wave tile beyond T: nothing is in range
             const int st_voff = (4 * h * p.Cout + l31) * 4;
             const bool st_on = DBG != 1 || p.T < 0;
             int row_bytes = p.Cout * 4;
@@ -707,12 +697,6 @@ __global__ __launch_bounds__(512, 2) void wino_zgemm_h2_kernel(WinoGemmArgs p) {
 }
 
 // ---- input transform into the pair layout ------------------------------------------------------------------------------
-__device__ __forceinline__ float wg_h_scale(unsigned amax_bits) {       // = wino_h3_scale (winograd.hip)
-    const float a = fminf(fmaxf(__uint_as_float(amax_bits), 1e-30f), 1e30f);
-    int e;
-    (void)frexpf(327.68f / a, &e);
-    return ldexpf(1.0f, e - 1);
-}
 __device__ __forceinline__ void wg_bt4(wf4 &d0, wf4 &d1, wf4 &d2, wf4 &d3, wf4 &d4, wf4 &d5) {   // = wino4_bt4
     const wf4 r0 = 4.0f * d0 - 5.0f * d2 + d4;
     const wf4 r1 = -4.0f * (d1 + d2) + d3 + d4;
@@ -721,15 +705,6 @@ __device__ __forceinline__ void wg_bt4(wf4 &d0, wf4 &d1, wf4 &d2, wf4 &d3, wf4 &
     const wf4 r4 = 2.0f * (d1 - d3) - d2 + d4;
     const wf4 r5 = 4.0f * d1 - 5.0f * d3 + d5;
     d0 = r0; d1 = r1; d2 = r2; d3 = r3; d4 = r4; d5 = r5;
-}
-
-template <int HI>
-__device__ __forceinline__ float wg_sub_half(float v, __half2 h) {       // v - (float)half HI of the packed pair h: one v_fma_mix_f32
-    float d;
-    const unsigned hb = *(const unsigned *)&h;
-    if (HI) asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    else asm("v_fma_mix_f32 %0, %1, -1.0, %2 op_sel:[0,0,0] op_sel_hi:[1,0,0]" : "=v"(d) : "v"(hb), "v"(v));
-    return d;
 }
 
 // V = B^T d B of every 6 x 6 input tile of x [B,H,W,C] (NHWC, times the power-of-two scale derived from *amax), split into
@@ -751,7 +726,7 @@ __global__ __launch_bounds__(256) void wino4_input_h2_kernel(const float *__rest
     const int ti = (int)((t / TW) % TH);
     const int b = (int)(t / ((int64_t)TW * TH));
     const int h0 = 4 * ti - 1, w0 = 4 * tj - 1;
-    const float sc = wg_h_scale(*amax);
+    const float sc = scale_le_327_68(__uint_as_float(*amax));
     wf4 d[6][6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -779,8 +754,8 @@ __global__ __launch_bounds__(256) void wino4_input_h2_kernel(const float *__rest
             const __half2 h0v = __floats2half2_rn(v.x, v.y), h1v = __floats2half2_rn(v.z, v.w);
             // v - (float)hi read in place out of the packed register (one v_fma_mix_f32 per value; through __half22float2 hipcc rounds
             // the value once more with a scalar conversion, converts back and subtracts)
-            const __half2 l0v = __floats2half2_rn(wg_sub_half<0>(v.x, h0v), wg_sub_half<1>(v.y, h0v));
-            const __half2 l1v = __floats2half2_rn(wg_sub_half<0>(v.z, h1v), wg_sub_half<1>(v.w, h1v));
+            const __half2 l0v = __floats2half2_rn(sub_half<0>(v.x, h0v), sub_half<1>(v.y, h0v));
+            const __half2 l1v = __floats2half2_rn(sub_half<0>(v.z, h1v), sub_half<1>(v.w, h1v));
             wu2 hi, lo;
             hi.x = *(const unsigned *)&h0v; hi.y = *(const unsigned *)&h1v;
             lo.x = *(const unsigned *)&l0v; lo.y = *(const unsigned *)&l1v;

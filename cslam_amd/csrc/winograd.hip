@@ -10,6 +10,7 @@
 // overlap is served by L2) and V / M are written / read exactly once.
 //   input  bytes per tile-channel: 16 B read (amortised) + 64 B written;   output: 64 B read + 16 B (4 B pooled) written
 #include "common.h"
+#include "pairs.h"
 #include <hip/hip_fp16.h>
 #include <cstdlib>
 
@@ -438,13 +439,7 @@ __global__ __launch_bounds__(256) void wino4_input_kernel(const float *__restric
 // A float times a power of two splits exactly into an fp16 pair hi + lo (11 + 11 significant bits); fp16 x fp16 products
 // are exact in the MFMA's fp32 accumulator, so  V U = vh uh + vl uh + vh ul  (the dropped vl ul is 2^-22 of the product)
 // is an fp32-grade product at the fp16 MFMA rate: one GEMM with K' = 3 Cin over  A' = [vh | vl | vh],  B' = [uh ; uh ; ul].
-// The scale keeps max |V| (<= 100 max |x| for B^T d B) below 2^15: s = 2^floor(log2(2^15 / (100 amax))).
-__device__ __forceinline__ float wino_h3_scale(unsigned amax_bits) {
-    const float a = fminf(fmaxf(__uint_as_float(amax_bits), 1e-30f), 1e30f);
-    int e;
-    (void)frexpf(327.68f / a, &e);                        // r = m 2^e, m in [0.5, 1): floor(log2 r) = e - 1
-    return ldexpf(1.0f, e - 1);
-}
+// The scale keeps max |V| (<= 100 max |x| for B^T d B) below 2^15: s = 2^floor(log2(2^15 / (100 amax))) (pairs.h::scale_le_327_68).
 
 // max |x| as float bits in *slot (non-negative floats order like their bit patterns); *slot must be 0 before the launch
 __global__ __launch_bounds__(256) void absmax_kernel(const float *__restrict__ x, int64_t n4, unsigned *__restrict__ slot) {
@@ -473,7 +468,7 @@ __global__ __launch_bounds__(256) void wino4_input_h3_kernel(const float *__rest
     const int ti = (int)((t / TW) % TH);
     const int b = (int)(t / ((int64_t)TW * TH));
     const int h0 = 4 * ti - 1, w0 = 4 * tj - 1;
-    const float sc = wino_h3_scale(*amax);
+    const float sc = scale_le_327_68(__uint_as_float(*amax));
     f2 d[6][6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -532,7 +527,7 @@ __global__ __launch_bounds__(256) void wino4_input_h3x4_kernel(const float *__re
     const int ti = (int)((t / TW) % TH);
     const int b = (int)(t / ((int64_t)TW * TH));
     const int h0 = 4 * ti - 1, w0 = 4 * tj - 1;
-    const float sc = wino_h3_scale(*amax);
+    const float sc = scale_le_327_68(__uint_as_float(*amax));
     wf4 d[6][6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) {
@@ -601,7 +596,7 @@ __global__ __launch_bounds__(256) void wino4_output_kernel(const float *__restri
     const int64_t plane = T * C;
     const float *p = M + t * C + 2 * c2;
     // split-fp16 GEMM (wino4_input_h3_kernel): M arrives times sV sU, both powers of two -> the rescale is exact
-    const float inv = amax ? inv_su / wino_h3_scale(*amax) : 1.0f;
+    const float inv = amax ? inv_su / scale_le_327_68(__uint_as_float(*amax)) : 1.0f;
     f2 s[4][6];
 #pragma unroll
     for (int j = 0; j < 6; ++j) {
@@ -683,7 +678,7 @@ __global__ __launch_bounds__(256) void wino4_output_z_kernel(const float *__rest
     const int64_t t = gid / c2n;
     const int64_t plane = T * C;
     const float *p = Zp + t * C + 2 * c2;
-    const float inv = amax ? inv_su / wino_h3_scale(*amax) : 1.0f;
+    const float inv = amax ? inv_su / scale_le_327_68(__uint_as_float(*amax)) : 1.0f;
     const f2 bv = bias ? *((const f2 *)bias + c2) : (f2)(0.0f);
     const int tj = (int)(t % TW);
     const int ti = (int)((t / TW) % TH);

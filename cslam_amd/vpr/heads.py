@@ -4,6 +4,7 @@ PyTorch is plumbing here (device memory + the current stream); the arithmetic is
 cslam_amd/csrc/heads.hip and gemm_nt.hip.  Every function requires CUDA(ROCm) tensors.
 """
 import ctypes as C
+import math
 
 import torch
 
@@ -98,6 +99,18 @@ def gem_fc_head(feat, p, eps, W, b):
     return out
 
 
+def pair_split(w):
+    """w (float64, or float32) -> (hi, lo, inv_s): the exact fp16 pair split of a weight operand (csrc/pairs.h).  s is the
+    power of two that brings max |w| into [2^14, 2^15) (1 when w is all zero); v = float32(s w) (exact for float32 weights),
+    hi = fp16(v), lo = fp16(v - hi): s w = hi + lo to 22 bits; inv_s = 1 / s.  The caller lays hi and lo out as its kernel reads them."""
+    amax = float(w.abs().max())
+    s = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
+    ws = (w * s).to(torch.float32)
+    hi = ws.to(torch.float16)
+    lo = (ws - hi.to(torch.float32)).to(torch.float16)
+    return hi, lo, 1.0 / s
+
+
 PCA_PAIR_SPLITS = 8             # K splits of the pair form of the projection (the "frequencies" of the pair GEMM): 8 vs 16 within 5 %
 PCA_PAIR_MIN_BATCH = 32         # below this the f32 forms (matrix-vector / f32-MFMA tile) are used
 
@@ -107,19 +120,13 @@ def pca_pair_weights(components, splits=PCA_PAIR_SPLITS):
     sW * components split into exact fp16 hi / lo pairs (sW the power of two that brings max |W| into [2^14, 2^15)), rows
     = output components, every 32-wide block of a row's K split holds its hi halves then its lo halves.  None when the
     shape does not fit (Din a multiple of 32 S, Dout of 128)."""
-    import math
     dout, din = components.shape
     if din % (32 * splits) or dout % 128:
         return None
-    w = components.detach().to(torch.float32)
-    amax = float(w.abs().max())
-    sw = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
-    ws = w * sw
-    wh = ws.to(torch.float16)
-    wl = (ws - wh.to(torch.float32)).to(torch.float16)
+    wh, wl, inv_sw = pair_split(components.detach().to(torch.float32))
     ks = din // splits
     pair = torch.stack((wh.view(dout, splits, ks // 32, 32), wl.view(dout, splits, ks // 32, 32)), dim=3)   # [Dout,S,kb,2,32]
-    return pair.permute(1, 0, 2, 3, 4).contiguous(), 1.0 / sw
+    return pair.permute(1, 0, 2, 3, 4).contiguous(), inv_sw
 
 
 def pca_project(x, components, mean_proj, inv_scale, pairs=None, x_bound=0.0):

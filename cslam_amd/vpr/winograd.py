@@ -12,14 +12,13 @@ The first convolution (3 input channels) stays on torch's direct form, with bias
 in one HIP pass (`cslam_bias_act_pool_dev`).
 """
 import ctypes as C
-import math
 import os
 
 import torch
 from torch import nn
 
 from .. import _lib
-from .heads import _p, _stream
+from .heads import _p, _stream, pair_split
 
 _G = torch.tensor([[1.0, 0.0, 0.0], [0.5, 0.5, 0.5], [0.5, -0.5, 0.5], [0.0, 0.0, 1.0]], dtype=torch.float64)
 _G4 = torch.tensor([[1 / 4, 0.0, 0.0], [-1 / 6, -1 / 6, -1 / 6], [-1 / 6, 1 / 6, -1 / 6],
@@ -40,12 +39,8 @@ def split16_weights(U4):
     split-fp16 GEMM (csrc/winograd.hip, `wino4_input_h3_kernel`): sU U = uh + ul exactly to 22 bits, sU the power of two
     that brings max |U| into [2^14, 2^15); inv_su = 1 / sU."""
     u = U4.detach().to(torch.float64)
-    amax = float(u.abs().max())
-    su = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
-    us = (u * su).to(torch.float32)                                  # exact: a power-of-two scale of float32 values
-    uh = us.to(torch.float16)
-    ul = (us - uh.to(torch.float32)).to(torch.float16)
-    return torch.cat((uh, uh, ul), dim=1).contiguous(), 1.0 / su
+    uh, ul, inv_su = pair_split(u)
+    return torch.cat((uh, uh, ul), dim=1).contiguous(), inv_su
 
 
 def split16_pair_weights(U4):
@@ -55,14 +50,10 @@ def split16_pair_weights(U4):
     n, cin, cout = U4.shape
     assert cin % 32 == 0
     u = U4.detach().to(torch.float64)
-    amax = float(u.abs().max())
-    su = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
-    us = (u * su).to(torch.float32)                                  # exact: a power-of-two scale of float32 values
-    uh = us.to(torch.float16)
-    ul = (us - uh.to(torch.float32)).to(torch.float16)
+    uh, ul, inv_su = pair_split(u)
     pair = torch.stack((uh, ul), dim=0)                              # [2, 36, Cin, Cout]
     pair = pair.view(2, n, cin // 32, 32, cout).permute(1, 4, 2, 0, 3)   # [36, Cout, Cin/32, 2, 32]
-    return pair.contiguous(), 1.0 / su
+    return pair.contiguous(), inv_su
 
 
 def direct_pair_weights(weight):
@@ -88,14 +79,10 @@ def igemm_pair_weights(weight):
     else:
         assert cin % 32 == 0
         k = w.reshape(cout, kh * kw * cin)
-    amax = float(k.abs().max())
-    sw = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
-    ks = (k * sw).to(torch.float32)
-    wh = ks.to(torch.float16)
-    wl = (ks - wh.to(torch.float32)).to(torch.float16)
+    wh, wl, inv_sw = pair_split(k)
     nk = k.shape[1] // 32
     pair = torch.stack((wh.view(cout, nk, 32), wl.view(cout, nk, 32)), dim=2)     # [Cout, nk, 2, 32]
-    return pair.contiguous(), 1.0 / sw
+    return pair.contiguous(), inv_sw
 
 
 def _pair(v):
@@ -242,14 +229,10 @@ def direct_r_pair_weights(weight):
     one v_mfma_f32_16x16x32_f16 A fragment per (q, tap, ks, mt, half), wave q of a workgroup holding [q] for the whole kernel."""
     assert tuple(weight.shape) == (128, 64, 3, 3)
     w = weight.detach().to(torch.float64)
-    amax = float(w.abs().max())
-    sw = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
-    ws = (w * sw).to(torch.float32)
-    wh = ws.to(torch.float16)
-    wl = (ws - wh.to(torch.float32)).to(torch.float16)
+    wh, wl, inv_sw = pair_split(w)
     pair = torch.stack((wh, wl), dim=0).reshape(2, 4, 2, 16, 2, 4, 8, 9)    # [hl][q][mt][i][ks][kg][e][tap]
     W2r = pair.permute(1, 7, 4, 2, 0, 5, 3, 6).reshape(4, 9, 2, 2, 2, 64, 8)  # [q][tap][ks][mt][hl][lane = 16 kg + i][e]
-    return W2r.contiguous(), 1.0 / sw
+    return W2r.contiguous(), inv_sw
 
 
 def conv3x3_direct_r(x, Wr, bias, relu, pool, amax_in, amax_out=None):
@@ -274,14 +257,10 @@ def direct_r2_pair_weights(weight):
     (tap, ks, slab, pair half), wave q of the workgroup that owns output-channel half `half` holding [half][q] for the whole kernel."""
     assert tuple(weight.shape) == (128, 128, 3, 3)
     w = weight.detach().to(torch.float64)
-    amax = float(w.abs().max())
-    sw = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
-    ws = (w * sw).to(torch.float32)
-    wh = ws.to(torch.float16)
-    wl = (ws - wh.to(torch.float32)).to(torch.float16)
+    wh, wl, inv_sw = pair_split(w)
     pair = torch.stack((wh, wl), dim=0).reshape(2, 2, 4, 16, 2, 2, 4, 8, 9)      # [hl][half][q][i][slab][ks][kg][e][tap]
     W2 = pair.permute(1, 2, 8, 5, 4, 0, 6, 3, 7).reshape(2, 4, 9, 2, 2, 2, 64, 8)  # [half][q][tap][ks][slab][hl][lane = 16 kg + i][e]
-    return W2.contiguous(), 1.0 / sw
+    return W2.contiguous(), inv_sw
 
 
 def conv3x3_direct_r2(x, Wr2, bias, relu, pool, amax_in, amax_out=None):
@@ -340,14 +319,10 @@ def fused64_pair_weights(U4):
     packed one dword per value, [uh | ul << 16], in the lane order of `fused64_weights`."""
     assert U4.shape[0] == 36 and U4.shape[1] == 64 and U4.shape[2] in (64, 128)
     u = U4.detach().to(torch.float64)
-    amax = float(u.abs().max())
-    su = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
-    us = (u * su).to(torch.float32)
-    uh = us.to(torch.float16)
-    ul = (us - uh.to(torch.float32)).to(torch.float16)
+    uh, ul, inv_su = pair_split(u)
     packed = (uh.view(torch.int16).to(torch.int32) & 0xFFFF) | (ul.view(torch.int16).to(torch.int32) << 16)
     cout = U4.shape[2]
-    return packed.view(36, 4, 4, 4, cout // 16, 16).permute(1, 0, 4, 2, 5, 3).contiguous(), 1.0 / su
+    return packed.view(36, 4, 4, 4, cout // 16, 16).permute(1, 0, 4, 2, 5, 3).contiguous(), inv_su
 
 
 def stem_pair_weights(weight):
@@ -359,11 +334,7 @@ def stem_pair_weights(weight):
     16 kq + n.  sumw[co] = sum |w[co]| (float64, rounded up to float32): the kernel bounds max |first-layer output| with it."""
     assert tuple(weight.shape) == (64, 3, 3, 3)
     w = weight.detach().to(torch.float64).cpu()
-    amax = float(w.abs().max())
-    sw = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
-    ws = (w * sw).to(torch.float32)
-    wh = ws.to(torch.float16)
-    wl = (ws - wh.to(torch.float32)).to(torch.float16)
+    wh, wl, inv_sw = pair_split(w)
     slots = torch.zeros((2, 64, 4, 8), dtype=torch.float16)              # [hi | lo][co][g][j]
     for g in range(3):
         for j in range(8):
@@ -376,7 +347,7 @@ def stem_pair_weights(weight):
     packed = bits[..., 0::2] | (bits[..., 1::2] << 16)                   # [2][64][4 g][4 d]
     W1 = packed.view(2, 4, 16, 4, 4).permute(1, 0, 3, 2, 4).reshape(4, 2, 64, 4).contiguous()   # [kq][hl][16 g + n][d]
     sumw = torch.nextafter(w.abs().sum(dim=(1, 2, 3)).to(torch.float32), torch.tensor(float("inf")))
-    return W1.to(weight.device), 1.0 / sw, sumw.to(weight.device).contiguous()
+    return W1.to(weight.device), inv_sw, sumw.to(weight.device).contiguous()
 
 
 def stem_direct_pair_weights(weight):
@@ -387,14 +358,10 @@ def stem_direct_pair_weights(weight):
     wave q of a workgroup -- the owner of output channels 16 q .. 16 q + 15 -- holding [q] for the whole kernel."""
     assert tuple(weight.shape) == (64, 64, 3, 3)
     w = weight.detach().to(torch.float64)
-    amax = float(w.abs().max())
-    sw = 2.0 ** (14 - math.floor(math.log2(amax))) if amax > 0 else 1.0
-    ws = (w * sw).to(torch.float32)
-    wh = ws.to(torch.float16)
-    wl = (ws - wh.to(torch.float32)).to(torch.float16)
+    wh, wl, inv_sw = pair_split(w)
     pair = torch.stack((wh, wl), dim=0).reshape(2, 4, 16, 2, 4, 8, 9)       # [hl][q][i][ks][kg][e][tap]
     W2r = pair.permute(1, 6, 3, 0, 4, 2, 5).reshape(4, 9, 2, 2, 64, 8)      # [q][tap][ks][hl][lane = 16 kg + i][e]
-    return W2r.contiguous(), 1.0 / sw
+    return W2r.contiguous(), inv_sw
 
 
 def conv_stem_direct_h(x0, stem, bias1, Wr, bias, pool, amax_x0, amax_out=None):

@@ -93,3 +93,97 @@ def test_normalised_image_bound_covers_every_8_bit_value():
     worst = max(float(np.abs((v - np.float32(m)) / np.float32(s)).max()) for m, s in zip(heads.IMAGENET_DEFAULT_MEAN,
                                                                                          heads.IMAGENET_DEFAULT_STD))
     assert worst <= b <= worst * 1.001
+
+
+def test_pair_split_scale_bracket_and_error():
+    """`heads.pair_split`, the one host split behind every weight packer: s a power of two with s max|w| in [2^14, 2^15),
+    |hi + lo - s w| <= 2^-21 s max|w|, s = 1 for an all-zero weight."""
+    torch.manual_seed(6)
+    for w in (torch.randn(64, 3, 3, 3, dtype=torch.float64) / 5.0, torch.randn(256, 2048) / 45.0,
+              torch.randn(36, 64, 128, dtype=torch.float64) * 300.0, torch.full((4, 32), 2.0 ** -20)):
+        hi, lo, inv_s = heads.pair_split(w)
+        s = 1.0 / inv_s
+        assert hi.dtype == torch.float16 and lo.dtype == torch.float16 and hi.shape == w.shape and lo.shape == w.shape
+        assert s == 2.0 ** round(np.log2(s))
+        sw = w.double() * s
+        smax = float(sw.abs().max())
+        assert 2.0 ** 14 <= smax < 2.0 ** 15
+        assert float((hi.double() + lo.double() - sw).abs().max()) <= 2.0 ** -21 * smax
+    hi, lo, inv_s = heads.pair_split(torch.zeros(8, 32, dtype=torch.float64))
+    assert inv_s == 1.0 and not hi.any() and not lo.any()
+
+
+def test_igemm_pair_weights_reassemble_in_k_block_order():
+    """`igemm_pair_weights` (csrc/conv_igemm.hip): W2[co][kb][hi | lo][j].  Cin = 3 (the 7x7 stem): block kb = kernel row kh, slot
+    j = kw * 3 + c, slots 3 KW .. 31 zero; Cin % 32 == 0: blocks in (kh, kw, Cin / 32) order, j = the channel inside the block."""
+    torch.manual_seed(7)
+    w = torch.randn(64, 3, 7, 7) / 12.0
+    W2, inv = wg.igemm_pair_weights(w)
+    assert W2.shape == (64, 7, 2, 32) and W2.dtype == torch.float16
+    rec = (W2[:, :, 0].double() + W2[:, :, 1].double()) * inv                                  # [co][kh][j]
+    want = torch.zeros(64, 7, 32, dtype=torch.float64)
+    for kh in range(7):
+        for kw in range(7):
+            for c in range(3):
+                want[:, kh, kw * 3 + c] = w[:, c, kh, kw].double()
+    assert float((rec - want).abs().max()) <= 2.0 ** -21 * float(w.abs().max())
+    assert not W2[:, :, :, 21:].any()
+    w = torch.randn(128, 64, 3, 3) / 24.0
+    W2, inv = wg.igemm_pair_weights(w)
+    assert W2.shape == (128, 18, 2, 32) and W2.dtype == torch.float16
+    rec = (W2[:, :, 0].double() + W2[:, :, 1].double()) * inv                                  # [co][kb][j]
+    want = torch.zeros(128, 18, 32, dtype=torch.float64)
+    for kh in range(3):
+        for kw in range(3):
+            for cb in range(2):
+                want[:, (kh * 3 + kw) * 2 + cb, :] = w[:, 32 * cb:32 * cb + 32, kh, kw].double()
+    assert float((rec - want).abs().max()) <= 2.0 ** -21 * float(w.abs().max())
+
+
+def test_direct_pair_weights_reassemble_in_tap_row_order():
+    """`direct_pair_weights` (csrc/conv_direct_h.hip): W2[ky * 3 + kx][co][kb][hi | lo][j] = the pair halves of w[co][32 kb + j][ky][kx]."""
+    torch.manual_seed(8)
+    w = torch.randn(128, 128, 3, 3) / 34.0
+    W2, inv = wg.direct_pair_weights(w)
+    assert W2.shape == (9, 128, 4, 2, 32) and W2.dtype == torch.float16
+    rec = (W2[:, :, :, 0].double() + W2[:, :, :, 1].double()) * inv                           # [tap][co][kb][j]
+    want = torch.stack([w[:, :, t // 3, t % 3].double() for t in range(9)]).reshape(9, 128, 4, 32)
+    assert float((rec - want).abs().max()) <= 2.0 ** -21 * float(w.abs().max())
+
+
+def test_direct_r2_pair_weights_are_in_mfma_lane_order():
+    """`direct_r2_pair_weights` (csrc/conv_direct_r.hip, conv3x3_direct_r2_kernel): W2r2[half][q][tap][ks][slab][hi | lo][lane][e] =
+    the pair halves of w[64 half + 16 q + lane % 16][64 slab + 32 ks + 8 (lane // 16) + e][tap // 3][tap % 3]."""
+    torch.manual_seed(9)
+    w = torch.randn(128, 128, 3, 3) / 34.0
+    W, inv = wg.direct_r2_pair_weights(w)
+    assert W.shape == (2, 4, 9, 2, 2, 2, 64, 8) and W.dtype == torch.float16
+    rec = (W[:, :, :, :, :, 0].double() + W[:, :, :, :, :, 1].double()) * inv                 # [half][q][tap][ks][slab][lane][e]
+    half, q, tap, ks, slab, lane, e = torch.meshgrid(*(torch.arange(n) for n in (2, 4, 9, 2, 2, 64, 8)), indexing="ij")
+    want = w.double()[64 * half + 16 * q + lane % 16, 64 * slab + 32 * ks + 8 * (lane // 16) + e, tap // 3, tap % 3]
+    assert float((rec - want).abs().max()) <= 2.0 ** -21 * float(w.abs().max())
+
+
+def test_fused64_pair_weights_pack_hi_lo_dwords_in_fused64_lane_order():
+    """`fused64_pair_weights` (csrc/wino_fused_h.hip): Uh[kq][xi][w][g][c][s] = [uh | ul << 16] of U[xi][16 kq + 4 g + s][16 w + c]."""
+    torch.manual_seed(10)
+    for cout in (64, 128):
+        U4 = wg.wino_weights(torch.randn(cout, 64, 3, 3) / 24.0, 4)
+        Uh, inv = wg.fused64_pair_weights(U4)
+        assert Uh.shape == (4, 36, cout // 16, 4, 16, 4) and Uh.dtype == torch.int32
+        lo16, hi16 = _halves(Uh.reshape(-1))                                               # low half: uh, high half: ul
+        rec = ((lo16.double() + hi16.double()) * inv).reshape(Uh.shape)
+        kq, xi, w_, g, c, s = torch.meshgrid(*(torch.arange(n) for n in Uh.shape), indexing="ij")
+        want = U4.double()[xi, 16 * kq + 4 * g + s, 16 * w_ + c]
+        assert float((rec - want).abs().max()) <= 2.0 ** -21 * float(U4.abs().max())
+
+
+def test_split16_weights_stack_hi_hi_lo():
+    """`split16_weights` (csrc/winograd.hip, the split-fp16 GEMM): U3[xi] = [uh ; uh ; ul] along K, uh + ul = sU U to 22 bits."""
+    torch.manual_seed(11)
+    U4 = torch.randn(36, 64, 128) / 8.0
+    U3, inv_su = wg.split16_weights(U4)
+    assert U3.shape == (36, 192, 128) and U3.dtype == torch.float16
+    assert torch.equal(U3[:, :64], U3[:, 64:128])
+    rec = (U3[:, :64].double() + U3[:, 128:].double()) * inv_su
+    assert float((rec - U4.double()).abs().max()) <= 2.0 ** -21 * float(U4.abs().max())

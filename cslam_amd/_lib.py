@@ -124,6 +124,7 @@ _SIGNATURES = {
     "cslam_conv3x3_c3_amax_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _vp, _vp, _vp]),
     "cslam_wino4_input_h2_dev": (_i, [_vp, _i, _i, _i, _i, _vp, _vp, _vp]),
     "cslam_wino_gemm_h2_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
+    "cslam_wino4_chain_h2_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _vp, C.c_float, _vp, C.c_float, C.c_float, _vp, _vp, _vp, _vp]),
     "cslam_wino_zgemm_h2_dev": (_i, [_vp, _vp, _i64, _i, _i, _vp, _vp]),
     "cslam_wino4_output_z_dev": (_i, [_vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),
     "cslam_conv_igemm_h2_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),

@@ -780,7 +780,13 @@ class _Step(object):
 #   fused_h          the one-kernel F(4x4) convolutions on fp16 pairs (csrc/wino_fused_h.hip); False: the f32-input MFMA kernels
 #   split16_min_cin  F(4x4) layers from that many input channels on run their 36 products on fp16 pairs (None: 128, or 256 with
 #                    split16_h3); 0: plain fp32 library GEMMs everywhere (bench.py's `value_fp32_gemms`)
-TRUNK_FORMS = {"conv_direct": 1, "conv_direct_r": True, "conv_direct_r2": True, "stem_direct": True, "wino_stem": True, "fused_h": True, "split16_min_cin": None}
+#   wino_chain       between two pair-product F(4x4) layers on the same map (ReLU, no pool), layer L's output transform and layer L + 1's
+#                    input transform as ONE kernel, y_L kept in LDS (csrc/wino_chain.hip); False: the two separate transforms
+TRUNK_FORMS = {"conv_direct": 1, "conv_direct_r": True, "conv_direct_r2": True, "stem_direct": True, "wino_stem": True, "fused_h": True, "split16_min_cin": None,
+               "wino_chain": True}
+# tile columns (ceil(W / 4)) of the maps whose boundaries take the chained transform: the classes measured faster than the output + input
+# pair at the 256-frame chunk
+CHAIN_TILE_COLS = (5, 16)
 FP32_GEMM_FORMS = {"split16_min_cin": 0, "fused_h": False, "wino_stem": False}      # the trunk on plain fp32 library GEMMs
 
 
@@ -862,6 +868,10 @@ class WinogradTrunk(_Workspace):
                     if m.in_channels == 128 and self.forms.get("conv_direct_r2", True):
                         st.Wdr2 = direct_r2_pair_weights(m.weight)
                 st.bias = None if m.bias is None else m.bias.detach().to(torch.float32).contiguous()
+                if st.U2 is not None and st.wl1 is None:
+                    # bound of the output, max|x| wl1 + bmax: the scale of the next layer's V when the chained transform writes it
+                    st.wl1 = float(m.weight.detach().abs().sum(dim=(1, 2, 3)).max())
+                    st.bmax = 0.0 if m.bias is None else float(m.bias.detach().abs().max())
                 i += 1
                 if i < len(mods) and isinstance(mods[i], nn.ReLU):
                     st.relu = True
@@ -910,6 +920,52 @@ class WinogradTrunk(_Workspace):
                         a.Wr = stem_direct_pair_weights(b.conv.weight)
         return self
 
+    def _chain_len(self, k, B, H, W):
+        """How many steps from step k on run as one chain (1: step k alone): consecutive layers that all take the pair-product branch
+        of `wino_conv3x3` on the same map, every one but the last with ReLU and neither pool nor Z form."""
+        t4h, t4w = -(-H // 4), -(-W // 4)
+        if not (self.forms["wino_chain"] and B * t4h * t4w >= 512 and 16 * t4h * t4w <= 1.35 * H * W
+                and CHAIN_TILE_COLS[0] <= t4w <= CHAIN_TILE_COLS[1]):
+            return 1
+        pair = lambda st_: (st_.kind == "wino" and st_.U2 is not None and st_.Wd is None and st_.Up is None       # noqa: E731
+                            and not _z_form(st_.conv.in_channels, st_.conv.out_channels))
+        n = 1
+        while (k + n < len(self.steps) and pair(self.steps[k + n - 1]) and pair(self.steps[k + n])
+               and self.steps[k + n - 1].relu and not self.steps[k + n - 1].pool):
+            n += 1
+        return n
+
+    def _run_chain(self, x, k, n, have, slots, want):
+        """Steps k .. k + n - 1 (`_chain_len`): input transform, then per layer the pair products and -- between two layers -- the chained
+        transform, which writes the next layer's V over the one the products have just read; the ordinary output transform ends the
+        chain.  slots[j] = max |input of step j| (measured by the kernel before it); bounds[j] = the bound step j's V was scaled by."""
+        lib = _lib.load()
+        B, Cin, H, W = x.shape
+        T = B * -(-H // 4) * -(-W // 4)
+        s = _stream(x)
+        if not have:
+            _lib.check(lib.cslam_absmax_dev(_p(x), x.numel(), _p(slots[k:k + 1]), s))
+        bounds = self._buf("chain_bounds", len(self.steps) + 1, x.device)
+        V2 = self._buf("V", 36 * T * Cin, x.device)
+        _lib.check(lib.cslam_wino4_input_h2_dev(_p(x), B, H, W, Cin, _p(slots[k:k + 1]), _p(V2), s))
+        vscale = slots[k:k + 1]
+        for j in range(k, k + n):
+            st = self.steps[j]
+            Cin, Cout = st.conv.in_channels, st.conv.out_channels
+            M = self._buf("M", 36 * T * Cout, x.device)
+            _lib.check(lib.cslam_wino_gemm_h2_dev(_p(V2), _p(st.U2[0]), T, Cin, Cout, _p(M), s))
+            bias = _p(st.bias) if st.bias is not None else None
+            if j + 1 < k + n:
+                V2 = self._buf("V", 36 * T * Cout, x.device)
+                _lib.check(lib.cslam_wino4_chain_h2_dev(_p(M), bias, B, H, W, Cout, _p(vscale), float(st.U2[1]), _p(slots[j:j + 1]),
+                                                        st.wl1, st.bmax, _p(slots[j + 1:j + 2]), _p(bounds[j + 1:j + 2]), _p(V2), s))
+                vscale = bounds[j + 1:j + 2]
+        Ho, Wo = (H // 2, W // 2) if st.pool else (H, W)
+        y = torch.empty((B, Cout, Ho, Wo), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
+        _lib.check(lib.cslam_wino4_output_scaled_dev(_p(M), bias, None, B, H, W, Cout, int(st.relu), int(st.pool), _p(vscale), float(st.U2[1]),
+                                                     _p(want) if want is not None else None, _p(y), s))
+        return y
+
     @torch.no_grad()
     def __call__(self, x):
         """x [B,C,H,W] float32 (any memory format) -> [B,C',H',W'] float32, channels_last memory."""
@@ -922,10 +978,10 @@ class WinogradTrunk(_Workspace):
         if any(wants(st) for st in self.steps):
             slots = self._buf("amax_slots", len(self.steps) + 1, x.device)
             slots.zero_()
-        skip = False
+        skip = 0
         for k, st in enumerate(self.steps):
-            if skip:                                                 # this step ran inside the previous one (stem kernel)
-                skip = False
+            if skip:                                                 # this step ran with the one before it (stem kernel, chained layers)
+                skip -= 1
                 continue
             have, amax_ready = amax_ready, None
             nxt = self.steps[k + 1] if k + 1 < len(self.steps) else None
@@ -948,7 +1004,7 @@ class WinogradTrunk(_Workspace):
                     else:
                         x = wino_stem64_h(x, st.stem, st.bias, nxt.Uph, nxt.bias, nxt.pool, slot, want)
                     amax_ready = want is not None
-                    skip = True
+                    skip = 1
                     continue
                 Cout = st.conv.out_channels
                 y = torch.empty((B, Cout, H, W), dtype=torch.float32, device=x.device, memory_format=torch.channels_last)
@@ -994,7 +1050,7 @@ class WinogradTrunk(_Workspace):
                     want2 = slots[k + 2:k + 3] if wants(nn2) else None
                     x = conv3x3_direct_hp(xp, (B_, 128, H_, W_), bslot, nxt.Wd, nxt.bias, nxt.relu, nxt.pool, want2)
                     amax_ready = want2 is not None
-                    skip = True
+                    skip = 1
                     continue
                 if st.Wdr is not None and x.shape[2] * x.shape[3] * 512 < 2 ** 31 - 16:
                     x = conv3x3_direct_r(x, st.Wdr, st.bias, st.relu, st.pool, slot, want)
@@ -1020,6 +1076,14 @@ class WinogradTrunk(_Workspace):
                     else:
                         x = wino_fused64(x, st.Up, st.bias, st.relu, st.pool)
                     continue
+            n = self._chain_len(k, x.shape[0], x.shape[2], x.shape[3])
+            if n > 1:
+                after = self.steps[k + n] if k + n < len(self.steps) else None
+                want = slots[k + n:k + n + 1] if wants(after) else None
+                x = self._run_chain(x, k, n, have, slots, want)
+                amax_ready = want is not None
+                skip = n - 1
+                continue
             want = slots[k + 1:k + 2] if wants(nxt) else None
             y = wino_conv3x3(self, x, st.U, st.U4, st.bias, st.relu, st.pool, U3=st.U3, U2=st.U2,
                              amax_in=slots[k:k + 1] if have else None, amax_out=want)

@@ -417,6 +417,15 @@ int cslam_wino4_output_scaled_dev(const float *d_M, const float *d_bias, const f
 int cslam_wino4_input_h2_dev(const float *d_x, int B, int H, int W, int C, const unsigned *d_amax, void *d_V2,
                              void *stream);
 int cslam_wino_gemm_h2_dev(const void *d_V2, const void *d_U2, int64_t T, int Cin, int Cout, float *d_M, void *stream);
+/* Output transform of layer L chained into the input transform of layer L + 1 on the same map (csrc/wino_chain.hip): what
+ * cslam_wino4_output_scaled_dev (ReLU, no pool, no residual) followed by cslam_wino4_input_h2_dev compute, with y_L kept in LDS.
+ * d_M [36][T][C] of layer L (C a multiple of 32, W <= 64); *d_vscale = the slot V_L was scaled by, inv_su as above;
+ * V2 of layer L + 1 is scaled by the power of two derived from the bound  *d_amax_x * wl1 + bmax  (*d_amax_x = bits of max |x_L|,
+ * wl1 = largest L1 norm of an output channel of layer L's 3x3 weights, bmax = max |bias|), which is stored in *d_bound_out: the
+ * d_amax of layer L + 1's output stage.  d_amax_out (zeroed by the caller) receives the bits of the measured max |y_L|. */
+int cslam_wino4_chain_h2_dev(const float *d_M, const float *d_bias, int B, int H, int W, int C, const unsigned *d_vscale,
+                             float inv_su, const unsigned *d_amax_x, float wl1, float bmax, unsigned *d_amax_out,
+                             unsigned *d_bound_out, void *d_V2, void *stream);
 /* The same products with the column half of the output transform Y = A^T M A folded in (the "Z form", for the layers whose
  * product is HBM-bound, Cin <= 256): d_Z [24][T][Cout] float32, plane 4 i + q = sum_j M[6 i + j] A^T[q][j] -- 2/3 of M's bytes
  * written and read.  cslam_wino4_output_z_dev finishes: Y[p][q] = sum_i A^T[p][i] Z_i[q], then the epilogue of

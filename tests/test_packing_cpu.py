@@ -187,3 +187,23 @@ def test_split16_weights_stack_hi_hi_lo():
     assert torch.equal(U3[:, :64], U3[:, 64:128])
     rec = (U3[:, :64].double() + U3[:, 128:].double()) * inv_su
     assert float((rec - U4.double()).abs().max()) <= 2.0 ** -21 * float(U4.abs().max())
+
+
+def test_winograd_namespace_keeps_every_name_bench_tests_and_tools_take_from_it():
+    """The packers live in vpr/pair_weights.py and the kernel wrappers in vpr/conv_kernels.py; bench.py, tests/ and tools/ reach all of
+    them, and the switches, through `cslam_amd.vpr.winograd` (`wg.X`, `wgm.X`, `winograd.X`, `from cslam_amd.vpr.winograd import X`):
+    every such name stays an attribute of that module."""
+    names = ("CHAIN_TILE_COLS", "DIRECT_P", "FP32_GEMM_FORMS", "PairAct", "TRUNK_FORMS", "VGG_PAIRS", "WinogradResNet", "WinogradTrunk",
+             "Z_FORM_MAX", "_Workspace", "conv3x3_direct_h", "conv3x3_direct_hp", "conv3x3_direct_p", "conv3x3_direct_r",
+             "conv3x3_direct_r2", "conv3x3_direct_r_pairs", "conv_igemm", "conv_igemm_p", "conv_stem_direct_h", "direct_p_fits",
+             "direct_pair_weights", "direct_r2_pair_weights", "direct_r_pair_weights", "fused64_pair_weights", "fused64_weights",
+             "igemm_pair_weights", "pairs_to_float", "split16_pair_weights", "split16_weights", "stem_direct_pair_weights",
+             "stem_pair_weights", "stem_pool_fits", "use_tuned_gemms", "wino_conv3x3", "wino_fused64", "wino_fused64_h", "wino_stem64_h",
+             "wino_weights")
+    # the switches the runners read at call time, which callers therefore set on this module, and the rest of its public surface
+    names += ("PAIR_ACTS", "IGEMM_CONVS", "fold_bn", "out_bound")
+    missing = [n for n in names if not hasattr(wg, n)]
+    assert not missing, missing
+    from cslam_amd.vpr import conv_kernels, pair_weights
+    for n in ("VGG_PAIRS", "Z_FORM_MAX", "PAIR_ACTS", "DIRECT_P", "IGEMM_CONVS", "TRUNK_FORMS", "CHAIN_TILE_COLS", "FP32_GEMM_FORMS"):
+        assert not hasattr(conv_kernels, n) and not hasattr(pair_weights, n), n     # one copy of every switch: the one callers set

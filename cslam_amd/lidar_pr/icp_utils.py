@@ -1,0 +1,288 @@
+#!/usr/bin/env python
+"""Relative transform between two lidar keyframes on an MI355X: batched point-to-point ICP.
+
+Counterpart of cslam/lidar_pr/icp_utils.py (`compute_transform`, called by lidar_handler_node.py:115,133 for every
+accepted ScanContext match).  The reference runs FPFH + mutual nearest neighbours + TEASER++ for a coarse alignment and
+then open3d's `registration_icp(src, dst, voxel_size, T, PointToPoint, max_iteration=100)` (icp_utils.py:126-134).
+Here the refinement keeps open3d's documented semantics exactly, and the coarse alignment comes from what this library
+already computes: the yaw shift of the ScanContext match (`ScanContextMatching.last_yaw_diff_deg`), helped by two
+coarse ICP stages at a larger correspondence radius (`DEFAULT_STAGES`).  FPFH and TEASER++ have no counterpart.
+
+The loop is hand-written HIP (csrc/icp.hip behind `cslam_icp_register_dev`): float64, brute-force nearest neighbours,
+fixed summation order -- a pair's result is the same bits alone or in any batch.  There is no CPU path: without the
+library or a GPU every registration raises `CslamHipError`.  Parity with open3d itself is not pinned (no open3d is
+available to record golden vectors from); the tests hold the kernels to a float64 restatement of open3d's documented
+algorithm.
+
+Clouds are [n, >=3] arrays or anything with a `.points` attribute (an open3d cloud); they are widened to float64 and
+rows with a non-finite coordinate are dropped, as the reference's `downsample` does.  Voxel down-sampling itself is
+not done here: the clouds the handler stores and sends are already down-sampled.
+
+Yaw seed: with `matcher.add_item(descriptor(dst))`, `matcher.search(descriptor(src))`, a source that is the target
+scene turned by +a degrees about z (dst ~ Rz(a) . src) matches at `last_yaw_diff_deg` = 360 - a (rounded to the 6 degree
+sector).  The seed is therefore the rotation about z by MINUS `init_yaw_deg`.
+"""
+import ctypes as C
+
+import numpy as np
+
+from .. import _lib
+
+# (multiple of voxel_size, max iterations) per stage; the last is the reference's refinement (icp_utils.py:126-131)
+DEFAULT_STAGES = ((4.0, 30), (2.0, 30), (1.0, 100))
+ICP_CHUNK = 1024      # target points per LDS chunk of the nearest-neighbour kernel (csrc/icp.hip); the tests size around it
+ICP_MAX_LANES = 64    # chunk lanes of its grid: a target of more chunks than this is walked lane-strided
+
+
+def Rt2T(R, t):
+    T = np.identity(4)
+    T[:3, :3] = R
+    T[:3, 3] = t
+    return T
+
+
+def yaw_seed(init_yaw_deg):
+    """4 x 4 initial transform for a ScanContext yaw shift in degrees (None -> identity): Rz(-init_yaw_deg)."""
+    if init_yaw_deg is None:
+        return np.identity(4)
+    a = np.deg2rad(-float(init_yaw_deg))
+    c, s = np.cos(a), np.sin(a)
+    return Rt2T(np.array([[c, -s, 0.0], [s, c, 0.0], [0.0, 0.0, 1.0]]), np.zeros(3))
+
+
+class RegistrationResult:
+    """open3d's RegistrationResult fields, plus the number of updates the (last) stage made."""
+
+    def __init__(self, transformation, fitness, inlier_rmse, correspondences, iterations, correspondence_set=None):
+        self.transformation = transformation
+        self.fitness = fitness
+        self.inlier_rmse = inlier_rmse
+        self.correspondences = correspondences
+        self.iterations = iterations
+        self.correspondence_set = correspondence_set
+
+    def __repr__(self):
+        return ("RegistrationResult(fitness=%.6f, inlier_rmse=%.6f, correspondences=%d, iterations=%d)"
+                % (self.fitness, self.inlier_rmse, self.correspondences, self.iterations))
+
+
+class Success:
+    """The success flag of `compute_transform`: truthy or falsy like the reference's bool, and it carries the figures
+    the decision was made from (`fitness`, `inlier_rmse`, `correspondences`, `iterations`, `transformation`)."""
+
+    def __init__(self, ok, result):
+        self.ok = bool(ok)
+        self.fitness = result.fitness
+        self.inlier_rmse = result.inlier_rmse
+        self.correspondences = result.correspondences
+        self.iterations = result.iterations
+        self.transformation = result.transformation
+
+    def __bool__(self):
+        return self.ok
+
+    def __repr__(self):
+        return "Success(%s, fitness=%.4f, inlier_rmse=%.4f, correspondences=%d)" % (
+            self.ok, self.fitness, self.inlier_rmse, self.correspondences)
+
+
+def _points(cloud):
+    pts = np.asarray(cloud.points if hasattr(cloud, "points") else cloud)
+    if pts.ndim != 2 or pts.shape[1] < 3:
+        raise ValueError("a cloud is an [n, >=3] array, got shape %s" % (pts.shape,))
+    pts = np.ascontiguousarray(pts[:, :3], dtype=np.float64)
+    return pts[np.isfinite(pts).all(axis=1)]
+
+
+def _register(pairs, inits, max_dists, max_iters, relative_fitness, relative_rmse, want_correspondences, device):
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    srcs = [_points(s) for s, _ in pairs]
+    dsts = [_points(d) for _, d in pairs]
+    n = len(pairs)
+    if n == 0:
+        return []
+    s_off = np.zeros(n + 1, dtype=np.int64)
+    d_off = np.zeros(n + 1, dtype=np.int64)
+    s_off[1:] = np.cumsum([len(c) for c in srcs])
+    d_off[1:] = np.cumsum([len(c) for c in dsts])
+    init = np.ascontiguousarray(np.stack([np.asarray(T, dtype=np.float64).reshape(4, 4) for T in inits]).reshape(n, 16))
+    dists = np.ascontiguousarray(max_dists, dtype=np.float64)
+    iters = np.ascontiguousarray(max_iters, dtype=np.int32)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_src = torch.from_numpy(np.concatenate(srcs, axis=0)).to(dev)
+        t_dst = torch.from_numpy(np.concatenate(dsts, axis=0)).to(dev)
+        t_so = torch.from_numpy(s_off).to(dev)
+        t_do = torch.from_numpy(d_off).to(dev)
+        t_init = torch.from_numpy(init).to(dev)
+        t_T = torch.empty((n, 16), dtype=torch.float64, device=dev)
+        t_stats = torch.empty((n, 4), dtype=torch.float64, device=dev)
+        st = torch.cuda.current_stream().cuda_stream
+        _lib.check(lib.cslam_icp_register_dev(
+            t_src.data_ptr(), t_so.data_ptr(), t_dst.data_ptr(), t_do.data_ptr(), n, t_init.data_ptr(),
+            dists.ctypes.data_as(C.c_void_p), iters.ctypes.data_as(C.c_void_p), len(dists), float(relative_fitness),
+            float(relative_rmse), t_T.data_ptr(), t_stats.data_ptr(), st))
+        t_idx = None
+        if want_correspondences:
+            t_idx = torch.empty(int(s_off[-1]), dtype=torch.int32, device=dev)
+            t_d2 = torch.empty(int(s_off[-1]), dtype=torch.float64, device=dev)
+            _lib.check(lib.cslam_icp_correspondences_dev(
+                t_src.data_ptr(), t_so.data_ptr(), t_dst.data_ptr(), t_do.data_ptr(), n, t_T.data_ptr(),
+                float(dists[-1]), t_idx.data_ptr(), t_d2.data_ptr(), st))
+        out = torch.cat((t_T, t_stats), dim=1).cpu().numpy()          # the one device -> host copy of the results
+        idx = t_idx.cpu().numpy() if t_idx is not None else None
+    results = []
+    for p in range(n):
+        corr = None
+        if idx is not None:
+            mine = idx[s_off[p]:s_off[p + 1]]
+            rows = np.nonzero(mine >= 0)[0]
+            corr = np.stack([rows, mine[rows].astype(np.int64)], axis=1)
+        results.append(RegistrationResult(out[p, :16].reshape(4, 4).copy(), float(out[p, 16]), float(out[p, 17]),
+                                          int(out[p, 18]), int(out[p, 19]), corr))
+    return results
+
+
+def nearest_correspondences(pairs, max_correspondence_distance, transformations=None, device=0):
+    """One evaluation for a list of (src, dst) pairs (`cslam_icp_correspondences_dev`): per pair (idx, dist2), where
+    idx[i] is the target row nearest to T . src[i] (ties -> the lower row), -1 when it is farther than the radius, and
+    dist2[i] its squared distance either way.  `transformations`: one 4 x 4 per pair, None = identity."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    pairs = [(_points(s), _points(d)) for s, d in pairs]
+    n = len(pairs)
+    if n == 0:
+        return []
+    s_off = np.zeros(n + 1, dtype=np.int64)
+    d_off = np.zeros(n + 1, dtype=np.int64)
+    s_off[1:] = np.cumsum([len(s) for s, _ in pairs])
+    d_off[1:] = np.cumsum([len(d) for _, d in pairs])
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_src = torch.from_numpy(np.concatenate([s for s, _ in pairs], axis=0)).to(dev)
+        t_dst = torch.from_numpy(np.concatenate([d for _, d in pairs], axis=0)).to(dev)
+        t_so = torch.from_numpy(s_off).to(dev)
+        t_do = torch.from_numpy(d_off).to(dev)
+        t_T = None
+        if transformations is not None:
+            t_T = torch.from_numpy(np.ascontiguousarray(
+                np.stack([np.asarray(T, dtype=np.float64).reshape(16) for T in transformations]))).to(dev)
+            assert t_T.shape == (n, 16)
+        t_idx = torch.empty(int(s_off[-1]), dtype=torch.int32, device=dev)
+        t_d2 = torch.empty(int(s_off[-1]), dtype=torch.float64, device=dev)
+        _lib.check(lib.cslam_icp_correspondences_dev(
+            t_src.data_ptr(), t_so.data_ptr(), t_dst.data_ptr(), t_do.data_ptr(), n,
+            t_T.data_ptr() if t_T is not None else None, float(max_correspondence_distance), t_idx.data_ptr(),
+            t_d2.data_ptr(), torch.cuda.current_stream().cuda_stream))
+        idx, d2 = t_idx.cpu().numpy(), t_d2.cpu().numpy()
+    return [(idx[s_off[p]:s_off[p + 1]], d2[s_off[p]:s_off[p + 1]]) for p in range(n)]
+
+
+def registration_icp(src, dst, max_correspondence_distance, init=np.eye(4), max_iteration=100, relative_fitness=1e-6,
+                     relative_rmse=1e-6, device=0):
+    """open3d.pipelines.registration.registration_icp with TransformationEstimationPointToPoint: one stage.
+    `transformation` maps source to target; `correspondence_set` is [n, 2] (source row, target row) at the result."""
+    return _register([(src, dst)], [init], [max_correspondence_distance], [max_iteration], relative_fitness,
+                     relative_rmse, True, device)[0]
+
+
+def register_pairs(pairs, voxel_size, init_yaw_deg=None, stages=DEFAULT_STAGES, correspondence_sets=False, device=0):
+    """Register a list of (src, dst) pairs in ONE batched call.  `init_yaw_deg`: None, one ScanContext yaw shift for
+    all pairs, or one per pair (entries may be None).  Stage s runs open3d's loop with the radius
+    stages[s][0] * voxel_size and at most stages[s][1] iterations from the previous stage's transform.  Returns one
+    `RegistrationResult` per pair (fitness, rmse, correspondences, iterations of the last stage)."""
+    pairs = list(pairs)
+    if init_yaw_deg is None or np.isscalar(init_yaw_deg):
+        yaws = [init_yaw_deg] * len(pairs)
+    else:
+        yaws = list(init_yaw_deg)
+        if len(yaws) != len(pairs):
+            raise ValueError("init_yaw_deg has %d entries for %d pairs" % (len(yaws), len(pairs)))
+    return _register(pairs, [yaw_seed(y) for y in yaws], [float(m) * voxel_size for m, _ in stages],
+                     [int(i) for _, i in stages], 1e-6, 1e-6, correspondence_sets, device)
+
+
+def _accept(result, min_inliers, min_fitness):
+    return result.correspondences > min_inliers and result.fitness >= min_fitness
+
+
+def solve_icp(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0):
+    """Counterpart of the reference's solve_teaser (icp_utils.py:103-139): (valid, translation, rotation) with
+    dst ~ rotation . src + translation."""
+    r = register_pairs([(src, dst)], voxel_size, init_yaw_deg)[0]
+    return _accept(r, min_inliers, min_fitness), r.transformation[:3, 3].copy(), r.transformation[:3, :3].copy()
+
+
+def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0):
+    """Computes a 3D transform between 2 point clouds (reference icp_utils.py:178-196), dst ~ R . src + t, as
+    registration_icp(source=src, target=dst) gives it.
+
+    Args:
+        src, dst: point clouds ([n, >=3] arrays or objects with `.points`), already down-sampled at voxel_size
+        voxel_size: correspondence radius of the final stage (the coarse stages use 4x and 2x)
+        min_inliers (int): the registration succeeds with MORE correspondences than this in the final stage ...
+        init_yaw_deg: `ScanContextMatching.last_yaw_diff_deg` of the match (None: start from the identity)
+        min_fitness: ... and a final fitness (correspondences / source points) of at least this
+
+    Returns:
+        (Transform, Success): the transform message and a success flag that is truthy / falsy like the reference's bool
+        and carries `fitness`, `inlier_rmse`, `correspondences`, `iterations` and the 4 x 4 `transformation`.
+
+    A correspondence count is a MUCH weaker test than the size of TEASER++'s maximum clique, which the reference
+    compares with min_inliers: the clique certifies mutually consistent matches, a count only says how many source points
+    have some target point within voxel_size.  A wrong alignment of two clouds that share a ground plane still has a
+    fitness of about 0.6 (thousands of "inliers"), a right one is above 0.9 on the same clouds.  Set `min_fitness`.
+    """
+    r = register_pairs([(src, dst)], voxel_size, init_yaw_deg)[0]
+    transform = to_transform_msg(r.transformation[:3, 3], r.transformation[:3, :3])
+    return transform, Success(_accept(r, min_inliers, min_fitness), r)
+
+
+def _quaternion(Rm):
+    """(x, y, z, w) of a rotation matrix: the largest of the four squared components first, the rest from the
+    off-diagonal sums (Shepperd's method)."""
+    m = np.asarray(Rm, dtype=np.float64)
+    d = [m[0, 0], m[1, 1], m[2, 2]]
+    four = [1 + d[0] - d[1] - d[2], 1 - d[0] + d[1] - d[2], 1 - d[0] - d[1] + d[2], 1 + d[0] + d[1] + d[2]]
+    k = int(np.argmax(four))
+    q = np.empty(4)
+    q[k] = 0.5 * np.sqrt(four[k])
+    f = 0.25 / q[k]
+    if k == 3:
+        q[0], q[1], q[2] = (m[2, 1] - m[1, 2]) * f, (m[0, 2] - m[2, 0]) * f, (m[1, 0] - m[0, 1]) * f
+    else:
+        i, j = (k + 1) % 3, (k + 2) % 3
+        q[i] = (m[i, k] + m[k, i]) * f
+        q[j] = (m[j, k] + m[k, j]) * f
+        q[3] = (m[j, i] - m[i, j]) * f
+    return q
+
+
+class _Vec:
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+class _Transform:
+    """Stand-in with the attributes of geometry_msgs.msg.Transform, for hosts without ROS."""
+
+    def __init__(self):
+        self.translation = _Vec(x=0.0, y=0.0, z=0.0)
+        self.rotation = _Vec(x=0.0, y=0.0, z=0.0, w=1.0)
+
+
+def to_transform_msg(translation, rotation):
+    """geometry_msgs.msg.Transform of (translation, rotation matrix) when ROS is importable (icp_utils.py:142-153),
+    else an object with the same `.translation.{x,y,z}` / `.rotation.{x,y,z,w}` attributes."""
+    try:
+        from geometry_msgs.msg import Transform
+    except ImportError:
+        Transform = _Transform
+    T = Transform()
+    T.translation.x, T.translation.y, T.translation.z = (float(v) for v in translation)
+    q = _quaternion(rotation)
+    T.rotation.x, T.rotation.y, T.rotation.z, T.rotation.w = (float(v) for v in q)
+    return T

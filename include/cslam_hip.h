@@ -364,6 +364,36 @@ int cslam_scancontext_from_cloud_dev(const double *d_points, const int64_t *d_of
                                      int rings, int sectors, double max_length, double *d_out,
                                      int32_t *d_status, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Lidar loop-closure registration: batched point-to-point ICP.
+ * Replaces the refinement of cslam/lidar_pr/icp_utils.py:126-134 (open3d registration_icp(src, dst, voxel_size, T,
+ * TransformationEstimationPointToPoint, ICPConvergenceCriteria(max_iteration=100))) for n_pairs (source, target)
+ * pairs at once.  Float64 throughout, brute-force nearest neighbours (ties -> lower target index).
+ * d_src / d_dst: the clouds concatenated, [total, 3]; pair p owns source rows d_src_off[p] .. d_src_off[p+1]-1 and
+ * target rows d_dst_off[p] .. d_dst_off[p+1]-1 (int64, n_pairs + 1 entries each, every cloud at least one point).
+ * The offsets are read back once (the only host wait) and every size is checked before anything is launched:
+ * CSLAM_E_INVALID on offsets that do not increase, a non-positive or non-finite radius, n_pairs outside [1, 65535].
+ * Results do not depend on which other pairs are in the batch (no atomics; every sum has one fixed order).
+ *
+ * correspondences: one evaluation at d_T ([n_pairs,16] row-major 4x4, NULL = identity).  d_idx[row] = the nearest
+ *   target point of T . src[row] (index within the pair's target cloud), -1 where its squared distance exceeds
+ *   max_dist^2; d_dist2[row] = that squared distance whether kept or not.  Both [total source rows]. */
+int cslam_icp_correspondences_dev(const double *d_src, const int64_t *d_src_off, const double *d_dst,
+                                  const int64_t *d_dst_off, int n_pairs, const double *d_T, double max_dist,
+                                  int32_t *d_idx, double *d_dist2, void *stream);
+/* register: open3d's loop (icp_utils.py:126-134), run as n_stages stages back to back; stage s uses the correspondence
+ *   radius max_dist[s] and at most max_iter[s] updates (host arrays), starts from the previous stage's transform
+ *   (stage 0 from d_init [n_pairs,16], NULL = identity) and stops a pair when |delta fitness| < rel_fitness and
+ *   |delta inlier_rmse| < rel_rmse between two evaluations (absolute differences, open3d's defaults 1e-6).
+ *   fitness = correspondences / source points, inlier_rmse = sqrt(sum d^2 / correspondences), both 0 without any.
+ *   Everything is enqueued on `stream` without a host wait; finished pairs cost an empty launch per round.
+ *   d_T_out [n_pairs,16]: source -> target.  d_stats_out [n_pairs,4]: fitness, inlier_rmse, correspondences and
+ *   iterations of the LAST stage. */
+int cslam_icp_register_dev(const double *d_src, const int64_t *d_src_off, const double *d_dst,
+                           const int64_t *d_dst_off, int n_pairs, const double *d_init, const double *max_dist,
+                           const int *max_iter, int n_stages, double rel_fitness, double rel_rmse, double *d_T_out,
+                           double *d_stats_out, void *stream);
+
 /* Winograd F(2x2, 3x3) transforms for the 3x3 / stride 1 / pad 1 convolutions of the extractor backbone
  * (the VGG-16 trunk built at cslam/vpr/netvlad.py:163-171; the reference runs it through torch's direct
  * convolution).  Activations are NHWC float32.  conv(x, g) + bias = output(bmm(input(x), U)) with

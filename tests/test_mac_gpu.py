@@ -115,10 +115,13 @@ def test_selection_with_gpu_solver_equals_reference(tag, R, K):
     assert np.array_equal(got, g7[tag + "/selected"])
 
 
-@pytest.mark.parametrize("m,bs", [(64, 64), (700, 64), (1000, 512), (5000, 2048), (4097, 2048)])
+@pytest.mark.parametrize("m,bs", [(64, 64), (700, 64), (1000, 512), (5000, 2048), (4097, 2048),
+                                  (1, 64), (63, 64), (65, 64), (513, 512), (4100, 4096)])
 def test_dense_cholesky_solve4_matches_library(m, bs):
     """cslam_chol_solve4_dev (the junction solve of every TraceMIN iteration) against torch.cholesky_solve, for both the
-    row-major factor of `blocked_cholesky_` and the column-major one library factorisations return; ragged last block."""
+    row-major factor of `blocked_cholesky_` and the column-major one library factorisations return; ragged last block.
+    m < 64 pads the staged block, m == bs + 1 leaves a trailing block of one row, bs = 4096 is the largest LDS request.  Each
+    factor is also passed as a view with ld = m + 7 into a wider buffer whose padding is NaN: a read outside the factor shows."""
     import torch
     from cslam_amd.mac.chain_solver_gpu import BlockedCholeskySolve, blocked_cholesky_
     g = torch.Generator(device="cuda").manual_seed(m)
@@ -130,12 +133,38 @@ def test_dense_cholesky_solve4_matches_library(m, bs):
     L_row = blocked_cholesky_(A.clone(), bs=256)                     # upper triangle keeps stale values: must never be read
     L_col = torch.tril(L_lib).T.contiguous().T                       # element (r, c) at c * m + r
     assert L_col.stride(0) == 1 and L_row.stride(1) == 1
-    for L in (L_row, L_col):
+    wide_row = torch.full((m, m + 7), float("nan"), device="cuda", dtype=torch.float64)
+    wide_row[:, :m] = L_row
+    wide_col = torch.full((m, m + 7), float("nan"), device="cuda", dtype=torch.float64)     # [column][row]
+    wide_col[:, :m] = L_col.T
+    L_row_ld, L_col_ld = wide_row[:, :m], wide_col[:, :m].T
+    if m > 1:
+        assert L_row_ld.stride() == (m + 7, 1) and L_col_ld.stride() == (1, m + 7)
+    for L in (L_row, L_col, L_row_ld, L_col_ld):
         x = BlockedCholeskySolve(L, bs).solve(rhs)
         assert float((x - ref).abs().max() / ref.abs().max()) < 1e-11
         assert float((A @ x - rhs).abs().max()) < 1e-9 * float(A.abs().max())
     x2 = BlockedCholeskySolve(L_row, bs).solve(rhs)                   # fixed summation order: bit-identical repeats
     assert torch.equal(x2, BlockedCholeskySolve(L_row, bs).solve(rhs))
+    assert torch.equal(x2, BlockedCholeskySolve(L_row_ld, bs).solve(rhs))   # the row stride changes no arithmetic
+
+
+def test_dense_cholesky_solve4_argument_errors_launch_nothing():
+    import torch
+    from cslam_amd import _lib
+    lib = _lib.load()
+    m = 100
+    f = lambda *shape: torch.full(shape, 77.0, device="cuda", dtype=torch.float64)
+    L, dinv, x, tmp = f(m, m), f(2, 64, 64), f(m, 4), f(4160, 4)
+    p = lambda t: C.c_void_p(t.data_ptr())
+    for bs, ld in ((32, m), (4160, m), (96, m), (0, m), (64, m - 1)):
+        for col_major in (0, 1):
+            assert lib.cslam_chol_solve4_dev(p(L), m, ld, col_major, p(dinv), p(dinv), bs, p(x), p(tmp), None) == -1
+            assert b"invalid argument" in lib.cslam_last_error()
+    assert lib.cslam_chol_solve4_dev(p(L), 0, m, 0, p(dinv), p(dinv), 64, p(x), p(tmp), None) == -1
+    assert lib.cslam_chol_solve4_dev(p(L), m, m, 0, p(dinv), p(dinv), 64, None, p(tmp), None) == -1
+    torch.cuda.synchronize()
+    assert int((x != 77.0).sum()) == 0 and int((tmp != 77.0).sum()) == 0
 
 
 def test_chain_gpu_fiedler_pair_is_reproducible_bit_for_bit():

@@ -116,6 +116,7 @@ _SIGNATURES = {
     "cslam_scancontext_from_cloud_dev": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp]),
     "cslam_icp_correspondences_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, C.c_double, _vp, _vp, _vp]),
     "cslam_icp_register_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "cslam_voxel_downsample_dev": (_i, [_vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_wino4_fused_c64_h_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_h_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_r_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),
@@ -149,12 +150,15 @@ _SIGNATURES = {
     "cslam_ring_schedule_describe": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int32 * 6), _vp, _i64, _vp, _vp, _vp]),
     "cslam_trunk_timing": (_i, [_i]),
     "cslam_trunk_timing_read": (_i, [C.POINTER(C.c_double * 8)]),
+    "cslam_voxel_profile": (_i, [_i]),
+    "cslam_voxel_profile_read": (_i, [C.POINTER(C.c_double * 6), C.POINTER(C.c_int32 * 4)]),
 }
 
 # declared in include/cslam_hip_experimental.h (A/B partners, profiling hooks, peak micro-benchmarks), not in the stable ABI
 EXPERIMENTAL_SYMBOLS = ("cslam_wino4_input_h3_dev", "cslam_wino2_fused64_dev", "cslam_wino2_fused_c64_dev",
                         "cslam_wino4_fused_c64_dev", "cslam_debug_wfh_prof_dev", "cslam_peak_copy_dev", "cslam_peak_mfma_dev",
-                        "cslam_debug_last_candidates", "cslam_ring_schedule_describe", "cslam_trunk_timing", "cslam_trunk_timing_read")
+                        "cslam_debug_last_candidates", "cslam_ring_schedule_describe", "cslam_trunk_timing", "cslam_trunk_timing_read",
+                        "cslam_voxel_profile", "cslam_voxel_profile_read")
 EXPORTED_SYMBOLS = tuple(n for n in _SIGNATURES if n not in EXPERIMENTAL_SYMBOLS)
 
 

@@ -15,8 +15,10 @@ available to record golden vectors from); the tests hold the kernels to a float6
 algorithm.
 
 Clouds are [n, >=3] arrays or anything with a `.points` attribute (an open3d cloud); they are widened to float64 and
-rows with a non-finite coordinate are dropped, as the reference's `downsample` does.  Voxel down-sampling itself is
-not done here: the clouds the handler stores and sends are already down-sampled.
+rows with a non-finite coordinate are dropped, as the reference's `downsample` does.  The clouds the handler stores
+and sends are down-sampled ones: `downsample` / `downsample_clouds` (csrc/voxel.hip behind
+`cslam_voxel_downsample_dev`) are the counterpart of the reference's `downsample` (icp_utils.py:93-100, open3d's
+`voxel_down_sample`), batched, and `keyframes.ingest` does it on the upload the ScanContext descriptor uses.
 
 Yaw seed: with `matcher.add_item(descriptor(dst))`, `matcher.search(descriptor(src))`, a source that is the target
 scene turned by +a degrees about z (dst ~ Rz(a) . src) matches at `last_yaw_diff_deg` = 360 - a (rounded to the 6 degree
@@ -32,6 +34,8 @@ from .. import _lib
 DEFAULT_STAGES = ((4.0, 30), (2.0, 30), (1.0, 100))
 ICP_CHUNK = 1024      # target points per LDS chunk of the nearest-neighbour kernel (csrc/icp.hip); the tests size around it
 ICP_MAX_LANES = 64    # chunk lanes of its grid: a target of more chunks than this is walked lane-strided
+VOXEL_TILE = 2048        # keys per workgroup per radix pass of the voxel sort (csrc/voxel_plan.h); the tests size around it
+VOXEL_SEG_BLOCK = 256    # threads per workgroup of the kernel that sums a voxel's points (one wave per voxel)
 
 
 def Rt2T(R, t):
@@ -92,6 +96,108 @@ def _points(cloud):
         raise ValueError("a cloud is an [n, >=3] array, got shape %s" % (pts.shape,))
     pts = np.ascontiguousarray(pts[:, :3], dtype=np.float64)
     return pts[np.isfinite(pts).all(axis=1)]
+
+
+def _rows(cloud):
+    """[n, 3] float64 rows of a cloud, non-finite rows included (the down-sampling kernels leave them out themselves)."""
+    pts = np.asarray(cloud.points if hasattr(cloud, "points") else cloud)
+    if pts.ndim != 2 or pts.shape[1] < 3:
+        raise ValueError("a cloud is an [n, >=3] array, got shape %s" % (pts.shape,))
+    return np.ascontiguousarray(pts[:, :3], dtype=np.float64)
+
+
+def _round256(n):
+    return (n + 255) // 256 * 256
+
+
+def _upload_clouds(clouds, dev):
+    """One host buffer, one copy: the int64 offsets, then the rows.  Returns (device bytes, host offsets, byte offset
+    of the rows)."""
+    import torch
+    n = len(clouds)
+    off = np.zeros(n + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(c) for c in clouds])
+    total, head = int(off[-1]), _round256(8 * (n + 1))
+    buf = np.zeros(head + 24 * total, dtype=np.uint8)
+    buf[:8 * (n + 1)].view(np.int64)[:] = off
+    if total:
+        np.concatenate(clouds, axis=0, out=buf[head:].view(np.float64).reshape(total, 3))
+    return torch.from_numpy(buf).to(dev), off, head
+
+
+def _voxel_enqueue(lib, t_in, off, head, voxel_size, counts, extra_bytes=0):
+    """`cslam_voxel_downsample_dev` on uploaded clouds.  Every result lies in ONE device byte buffer, so that it comes
+    back in one copy: returns (buffer, layout) with layout = byte offsets of out_offsets, status, rows, counts, extra."""
+    import torch
+    n, total = len(off) - 1, int(off[-1])
+    lay = {"out_off": 0}
+    lay["status"] = _round256(8 * (n + 1))
+    lay["rows"] = lay["status"] + _round256(4 * n)
+    lay["counts"] = lay["rows"] + _round256(24 * total)
+    lay["extra"] = lay["counts"] + _round256(4 * total if counts else 0)
+    t_out = torch.zeros(lay["extra"] + extra_bytes, dtype=torch.uint8, device=t_in.device)
+    base = t_out.data_ptr()
+    _lib.check(lib.cslam_voxel_downsample_dev(
+        t_in.data_ptr() + head if total else None, t_in.data_ptr(), n, float(voxel_size),
+        base + lay["rows"] if total else None, base + lay["out_off"], base + lay["counts"] if counts and total else None,
+        base + lay["status"], off.ctypes.data_as(C.c_void_p), torch.cuda.current_stream().cuda_stream))
+    return t_out, lay
+
+
+class VoxelSizeError(ValueError):
+    """A cloud needs a voxel index of 2^21 or more on some axis.  `failed`: the numbers of those clouds; `clouds`: the
+    results of the call with None in their places (the other clouds of a batch are not affected)."""
+
+    def __init__(self, failed, clouds):
+        ValueError.__init__(self, "voxel_size is too small for cloud%s %s: a voxel index of 2^21 or more on some axis "
+                            "(open3d raises 'voxel_size is too small' where its index arithmetic overflows)"
+                            % ("s" if len(failed) > 1 else "", ", ".join(str(c) for c in failed)))
+        self.failed = failed
+        self.clouds = clouds
+
+
+def _voxel_unpack(host, lay, n, counts):
+    """Split the downloaded result buffer into per-cloud arrays; raises VoxelSizeError for a status of 1."""
+    out_off = host[lay["out_off"]:lay["out_off"] + 8 * (n + 1)].view(np.int64)
+    status = host[lay["status"]:lay["status"] + 4 * n].view(np.int32)
+    m = int(out_off[-1])
+    rows = host[lay["rows"]:lay["rows"] + 24 * m].view(np.float64).reshape(m, 3)
+    cnt = host[lay["counts"]:lay["counts"] + 4 * m].view(np.int32) if counts else None
+    res = []
+    for c in range(n):
+        a, b = int(out_off[c]), int(out_off[c + 1])
+        pts = rows[a:b].copy()
+        res.append((pts, cnt[a:b].astype(np.int64)) if counts else pts)
+    failed = [c for c in range(n) if status[c] != 0]
+    if failed:
+        raise VoxelSizeError(failed, [None if c in failed else r for c, r in enumerate(res)])
+    return res
+
+
+def downsample_clouds(clouds, voxel_size, counts=False, device=0):
+    """Voxel down-sampling of a list of clouds in ONE call (one upload, one download): per cloud the [m, 3] float64
+    means of the occupied voxels, in ascending lexicographic voxel index; with `counts` a pair (means, points per
+    voxel).  The rule is open3d's `voxel_down_sample` after the reference's filter of non-finite rows
+    (icp_utils.py:93-100); the filter too runs on the GPU.  A cloud without a finite row gives [0, 3].
+    Raises `VoxelSizeError` (a ValueError) naming the clouds whose index range is beyond 2^21 per axis."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    clouds = [_rows(c) for c in clouds]
+    if not clouds:
+        return []
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_in, off, head = _upload_clouds(clouds, dev)
+        t_out, lay = _voxel_enqueue(lib, t_in, off, head, voxel_size, counts)
+        host = t_out.cpu().numpy()
+    return _voxel_unpack(host, lay, len(clouds), counts)
+
+
+def downsample(points, voxel_size, device=0):
+    """Counterpart of the reference's `downsample` (icp_utils.py:93-100): the down-sampled cloud as an [m, 3] float64
+    array (every function of this module takes arrays or `.points`)."""
+    return downsample_clouds([points], voxel_size, device=device)[0]
 
 
 def _register(pairs, inits, max_dists, max_iters, relative_fitness, relative_rmse, want_correspondences, device):
@@ -221,7 +327,7 @@ def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_
     registration_icp(source=src, target=dst) gives it.
 
     Args:
-        src, dst: point clouds ([n, >=3] arrays or objects with `.points`), already down-sampled at voxel_size
+        src, dst: point clouds ([n, >=3] arrays or objects with `.points`) as `downsample(cloud, voxel_size)` returns them
         voxel_size: correspondence radius of the final stage (the coarse stages use 4x and 2x)
         min_inliers (int): the registration succeeds with MORE correspondences than this in the final stage ...
         init_yaw_deg: `ScanContextMatching.last_yaw_diff_deg` of the match (None: start from the identity)

@@ -17,6 +17,12 @@ import numpy as np
 from .. import _lib
 
 
+def theta_360_error(sectors):
+    """The reference's failure for a point at exactly 360 degrees (ptcloud2sc indexes sector `sectors`)."""
+    return IndexError("index %d is out of bounds for axis 2 with size %d (a point at exactly 360 degrees, "
+                      "as in the reference's ptcloud2sc)" % (sectors, sectors))
+
+
 class ScanContext:
     """
     Scan Context descriptor for point clouds
@@ -53,6 +59,5 @@ class ScanContext:
                 float(self.max_length), out.data_ptr(), status.data_ptr(), st))
         res = out.cpu().numpy()
         if int(status.item()) != 0:
-            raise IndexError("index %d is out of bounds for axis 2 with size %d (a point at exactly 360 degrees, "
-                             "as in the reference's ptcloud2sc)" % (self.shape[1], self.shape[1]))
+            raise theta_360_error(self.shape[1])
         return res

@@ -394,6 +394,28 @@ int cslam_icp_register_dev(const double *d_src, const int64_t *d_src_off, const 
                            const int *max_iter, int n_stages, double rel_fitness, double rel_rmse, double *d_T_out,
                            double *d_stats_out, void *stream);
 
+/* Lidar keyframes: batched voxel down-sampling, the step every keyframe goes through before it is stored
+ * (cslam/lidar_pr/icp_utils.py:93-100 `downsample`: drop the rows with a non-finite coordinate, then open3d's
+ * voxel_down_sample; called by lidar_handler_node.py:180).  Per cloud, in float64: origin = min over the finite rows
+ * - voxel / 2 per axis, voxel index = floor((p - origin) / voxel), one output row per occupied voxel = the sum of its
+ * points in cloud order, accumulated one after another from the first, divided once by their number.  Rows come in
+ * ascending lexicographic voxel index, x most significant (open3d's own order is that of a hash map).  The result does
+ * not depend on which other clouds are in the batch (no float atomics; every sum has one fixed order).
+ * d_points: the clouds concatenated, [total, 3]; cloud c owns rows d_offsets[c] .. d_offsets[c+1]-1 (int64,
+ *   n_clouds + 1 entries from 0; empty clouds are allowed).  h_offsets: a host copy of the same offsets, or NULL.
+ * d_out [total, 3] has the capacity of the input; cloud c's rows are d_out_offsets[c] .. d_out_offsets[c+1]-1
+ *   (n_clouds + 1 entries, written on the device).  d_counts: NULL, or [total]: the points of every output row.
+ * d_status [n_clouds]: 0, or 1 for a cloud with a voxel index of 2^21 or more on some axis (open3d: "voxel_size is too
+ *   small"): it gets no rows.  A cloud without a finite row gets no rows and status 0.
+ * CSLAM_E_INVALID, before anything touches HIP: voxel not finite or <= 0, n_clouds outside [1, 65535], host offsets
+ *   that do not start at 0 or that decrease (device-only offsets are checked after the wait).
+ * Scratch is the library's own, per (device, stream).  The call waits on the host once, after the per-cloud bounds:
+ *   it reads the widest voxel key of the batch and whether any row is left out (8 bytes, which select the sort passes),
+ *   and the offsets when h_offsets is NULL.  Everything after that is enqueued on `stream` without a wait. */
+int cslam_voxel_downsample_dev(const double *d_points, const int64_t *d_offsets, int n_clouds, double voxel,
+                               double *d_out, int64_t *d_out_offsets, int32_t *d_counts, int32_t *d_status,
+                               const int64_t *h_offsets, void *stream);
+
 /* Winograd F(2x2, 3x3) transforms for the 3x3 / stride 1 / pad 1 convolutions of the extractor backbone
  * (the VGG-16 trunk built at cslam/vpr/netvlad.py:163-171; the reference runs it through torch's direct
  * convolution).  Activations are NHWC float32.  conv(x, g) + bias = output(bmm(input(x), U)) with

@@ -60,6 +60,13 @@ int cslam_peak_mfma_dev(int kind, int iters, int blocks, int operands, float *d_
 int cslam_trunk_timing(int enable);
 int cslam_trunk_timing_read(double out[8]);
 
+/* Stage times of cslam_voxel_downsample_dev (tools/perf_voxel.py): while enabled every call records HIP events on its stream at
+ * its stage boundaries.  cslam_voxel_profile_read waits for the last profiled call and gives ms = {bounds + meta, the host wait,
+ * keys, radix passes, segment heads + scan + offsets, segment sums} and info = {key passes, cloud-number passes, key bits
+ * (the "row left out" bit included), sort tiles}. */
+int cslam_voxel_profile(int enable);
+int cslam_voxel_profile_read(double ms[6], int32_t info[4]);
+
 /* The candidate lists stage 1 of the last MFMA-mode search of `bank` left in its workspace (valid until the bank's next
  * search): keys [nq][*nseg][16] float32 in units of q.b / ||b|| (sorted per segment, -inf = empty), rows [nq][*nseg][16]
  * (-1 = empty), and the bound on |key - exact| / ||q|| handed to the float64 certificate.  tests/test_nns_gpu.py checks the

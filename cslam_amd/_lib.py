@@ -117,6 +117,10 @@ _SIGNATURES = {
     "cslam_icp_correspondences_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, C.c_double, _vp, _vp, _vp]),
     "cslam_icp_register_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
     "cslam_voxel_downsample_dev": (_i, [_vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_knn_radius_dev": (_i, [_vp, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_normals_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp]),
+    "cslam_fpfh_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    "cslam_feature_match_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_wino4_fused_c64_h_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_h_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_r_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),

@@ -1,12 +1,16 @@
 #!/usr/bin/env python
-"""Relative transform between two lidar keyframes on an MI355X: batched point-to-point ICP.
+"""Relative transform between two lidar keyframes on an MI355X: batched point-to-point ICP, and the FPFH features and
+mutual matches a robust coarse fit starts from.
 
 Counterpart of cslam/lidar_pr/icp_utils.py (`compute_transform`, called by lidar_handler_node.py:115,133 for every
 accepted ScanContext match).  The reference runs FPFH + mutual nearest neighbours + TEASER++ for a coarse alignment and
 then open3d's `registration_icp(src, dst, voxel_size, T, PointToPoint, max_iteration=100)` (icp_utils.py:126-134).
 Here the refinement keeps open3d's documented semantics exactly, and the coarse alignment comes from what this library
 already computes: the yaw shift of the ScanContext match (`ScanContextMatching.last_yaw_diff_deg`), helped by two
-coarse ICP stages at a larger correspondence radius (`DEFAULT_STAGES`).  FPFH and TEASER++ have no counterpart.
+coarse ICP stages at a larger correspondence radius (`DEFAULT_STAGES`).  `extract_fpfh` and `find_correspondences`
+(icp_utils.py:26-65) have counterparts of the same names here (csrc/fpfh.hip, batched forms `extract_fpfh_clouds` and
+`find_correspondences_pairs`): they produce putative correspondences that do not come from the alignment under test.
+TEASER++, the robust fit that would consume them, has no counterpart yet, and `compute_transform` does not use them.
 
 The loop is hand-written HIP (csrc/icp.hip behind `cslam_icp_register_dev`): float64, brute-force nearest neighbours,
 fixed summation order -- a pair's result is the same bits alone or in any batch.  There is no CPU path: without the
@@ -36,6 +40,15 @@ ICP_CHUNK = 1024      # target points per LDS chunk of the nearest-neighbour ker
 ICP_MAX_LANES = 64    # chunk lanes of its grid: a target of more chunks than this is walked lane-strided
 VOXEL_TILE = 2048        # keys per workgroup per radix pass of the voxel sort (csrc/voxel_plan.h); the tests size around it
 VOXEL_SEG_BLOCK = 256    # threads per workgroup of the kernel that sums a voxel's points (one wave per voxel)
+KNN_BLOCK = 256       # threads per workgroup of the radius search (csrc/fpfh.hip): one wave per query point, four per workgroup
+KNN_CHUNK = 1024      # cloud points per LDS chunk of the radius search; the tests size around it
+KNN_CAND = 512        # candidate buffer of a query: more in-radius points than this are cut to the best max_nn - 1 on the way
+KNN_MAX_NN = 256      # widest neighbour list
+FM_BLOCK = 64         # query rows per workgroup of the feature matching kernel
+FM_CHUNK = 32         # target rows per LDS chunk of the feature matching kernel
+FM_MAX_LANES = 16     # chunk lanes of its grid: a target of more chunks than this is walked lane-strided
+FM_MAX_DIM = 64       # widest feature
+FPFH_BINS = 33
 
 
 def Rt2T(R, t):
@@ -198,6 +211,209 @@ def downsample(points, voxel_size, device=0):
     """Counterpart of the reference's `downsample` (icp_utils.py:93-100): the down-sampled cloud as an [m, 3] float64
     array (every function of this module takes arrays or `.points`)."""
     return downsample_clouds([points], voxel_size, device=device)[0]
+
+
+# ---- FPFH features and mutual matches (csrc/fpfh.hip) ---------------------------------------------------------------
+def _stream():
+    import torch
+    return torch.cuda.current_stream().cuda_stream
+
+
+def _host(off):
+    return off.ctypes.data_as(C.c_void_p)
+
+
+def _knn_enqueue(lib, t_in, off, head, radius, max_nn):
+    """`cslam_knn_radius_dev` on uploaded clouds (at least one point in all): device (idx, d2, count)."""
+    import torch
+    total, dev = int(off[-1]), t_in.device
+    t_idx = torch.empty((total, max_nn), dtype=torch.int32, device=dev)
+    t_d2 = torch.empty((total, max_nn), dtype=torch.float64, device=dev)
+    t_cnt = torch.empty(total, dtype=torch.int32, device=dev)
+    _lib.check(lib.cslam_knn_radius_dev(t_in.data_ptr() + head, t_in.data_ptr(), len(off) - 1, float(radius), int(max_nn),
+                                        t_idx.data_ptr(), t_d2.data_ptr(), t_cnt.data_ptr(), _host(off), _stream()))
+    return t_idx, t_d2, t_cnt
+
+
+def _normals_enqueue(lib, t_in, off, head, lists, radius, max_nn, viewpoint):
+    import torch
+    t_idx, t_d2, t_cnt = lists
+    view = np.ascontiguousarray(viewpoint, dtype=np.float64).reshape(3)
+    t_n = torch.empty((int(off[-1]), 3), dtype=torch.float64, device=t_in.device)
+    _lib.check(lib.cslam_normals_dev(t_in.data_ptr() + head, t_in.data_ptr(), len(off) - 1, t_idx.data_ptr(), t_d2.data_ptr(),
+                                     t_cnt.data_ptr(), t_idx.shape[1], float(radius), int(max_nn), _host(view), t_n.data_ptr(),
+                                     _host(off), _stream()))
+    return t_n
+
+
+def _fpfh_enqueue(lib, t_in, off, head, t_normals, lists, spfh):
+    """Device [total, 33] FPFH, or [2, total, 33] (FPFH, SPFH) with `spfh`."""
+    import torch
+    t_idx, t_d2, t_cnt = lists
+    total = int(off[-1])
+    t_f = torch.empty((2 if spfh else 1, total, FPFH_BINS), dtype=torch.float64, device=t_in.device)
+    _lib.check(lib.cslam_fpfh_dev(t_in.data_ptr() + head, t_normals.data_ptr(), t_in.data_ptr(), len(off) - 1, t_idx.data_ptr(),
+                                  t_d2.data_ptr(), t_cnt.data_ptr(), t_idx.shape[1], t_f.data_ptr(),
+                                  t_f[1].data_ptr() if spfh else None, _host(off), _stream()))
+    return t_f if spfh else t_f[0]
+
+
+def _split(rows, off):
+    return [rows[int(off[c]):int(off[c + 1])].copy() for c in range(len(off) - 1)]
+
+
+def radius_neighbors_clouds(clouds, radius, max_nn, device=0):
+    """The neighbour lists the normals and the features are computed from (`cslam_knn_radius_dev`, the counterpart of
+    open3d's KDTreeSearchParamHybrid(radius, max_nn)) for a list of clouds in one call: per cloud (idx [n, max_nn] int32,
+    d2 [n, max_nn], count [n]).  The list of point i is i itself, then the other points within the radius in ascending
+    (d2, index), `max_nn` entries at most; beyond the count idx is -1 and d2 is +inf."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    clouds = [_points(c) for c in clouds]
+    if sum(len(c) for c in clouds) == 0:
+        if not (np.isfinite(radius) and radius > 0 and 1 <= max_nn <= KNN_MAX_NN):
+            raise _lib.CslamHipError("invalid argument: radius must be positive and finite, max_nn in [1, %d]" % KNN_MAX_NN)
+        return [(np.zeros((0, max_nn), np.int32), np.zeros((0, max_nn)), np.zeros(0, np.int32)) for _ in clouds]
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_in, off, head = _upload_clouds(clouds, dev)
+        idx, d2, cnt = (t.cpu().numpy() for t in _knn_enqueue(lib, t_in, off, head, radius, max_nn))
+    return list(zip(_split(idx, off), _split(d2, off), _split(cnt, off)))
+
+
+def radius_neighbors(cloud, radius, max_nn, device=0):
+    return radius_neighbors_clouds([cloud], radius, max_nn, device)[0]
+
+
+def estimate_normals_clouds(clouds, radius, max_nn=30, viewpoint=(0.0, 0.0, 0.0), device=0):
+    """open3d's `estimate_normals(KDTreeSearchParamHybrid(radius, max_nn))` for a list of clouds in one call: per cloud
+    the [n, 3] unit normals.  The eigenvector of the smallest eigenvalue of the neighbours' covariance; (0, 0, 1) with
+    fewer than 3 neighbours (the point included).  The sign is fixed, which open3d leaves to its eigen-solver: every
+    normal points to the side of `viewpoint` (default: the sensor at the origin of a keyframe cloud)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    clouds = [_points(c) for c in clouds]
+    if sum(len(c) for c in clouds) == 0:
+        return [np.zeros((0, 3)) for _ in clouds]
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_in, off, head = _upload_clouds(clouds, dev)
+        lists = _knn_enqueue(lib, t_in, off, head, radius, max_nn)
+        normals = _normals_enqueue(lib, t_in, off, head, lists, radius, max_nn, viewpoint).cpu().numpy()
+    return _split(normals, off)
+
+
+def estimate_normals(cloud, radius, max_nn=30, viewpoint=(0.0, 0.0, 0.0), device=0):
+    return estimate_normals_clouds([cloud], radius, max_nn, viewpoint, device)[0]
+
+
+def compute_fpfh_feature(cloud, normals, radius, max_nn=100, return_spfh=False, device=0):
+    """open3d's `compute_fpfh_feature(cloud, KDTreeSearchParamHybrid(radius, max_nn))` with the normals given: the
+    [n, 33] features, one ROW per point (the reference transposes open3d's [33, n], icp_utils.py:37); with
+    `return_spfh` the pair (FPFH, SPFH)."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    pts = _points(cloud)
+    nrm = np.ascontiguousarray(normals, dtype=np.float64)
+    if nrm.shape != pts.shape:
+        raise ValueError("normals of shape %s for %d points with finite coordinates" % (nrm.shape, len(pts)))
+    if len(pts) == 0:
+        return (np.zeros((0, FPFH_BINS)),) * 2 if return_spfh else np.zeros((0, FPFH_BINS))
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_in, off, head = _upload_clouds([pts], dev)
+        lists = _knn_enqueue(lib, t_in, off, head, radius, max_nn)
+        out = _fpfh_enqueue(lib, t_in, off, head, torch.from_numpy(nrm).to(dev), lists, return_spfh).cpu().numpy()
+    return (out[0], out[1]) if return_spfh else out
+
+
+def extract_fpfh_clouds(clouds, voxel_size, viewpoint=(0.0, 0.0, 0.0), device=0):
+    """`extract_fpfh` for a list of clouds in ONE call (one upload, one download).  One neighbour search at
+    (5 voxels, 100) serves both steps: the normals at (2 voxels, 30) use the prefix of each list, which is the list a
+    search of their own returns."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    clouds = [_points(c) for c in clouds]
+    if sum(len(c) for c in clouds) == 0:
+        return [np.zeros((0, FPFH_BINS)) for _ in clouds]
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_in, off, head = _upload_clouds(clouds, dev)
+        lists = _knn_enqueue(lib, t_in, off, head, 5.0 * voxel_size, 100)
+        t_n = _normals_enqueue(lib, t_in, off, head, lists, 2.0 * voxel_size, 30, viewpoint)
+        feats = _fpfh_enqueue(lib, t_in, off, head, t_n, lists, False).cpu().numpy()
+    return _split(feats, off)
+
+
+def extract_fpfh(cloud, voxel_size, viewpoint=(0.0, 0.0, 0.0), device=0):
+    """Counterpart of the reference's `extract_fpfh` (icp_utils.py:26-37): normals from the neighbours within 2 voxels
+    (30 at most), FPFH from those within 5 voxels (100 at most); [n, 33] float64."""
+    return extract_fpfh_clouds([cloud], voxel_size, viewpoint, device)[0]
+
+
+def _features(x):
+    f = np.ascontiguousarray(x, dtype=np.float64)
+    if f.ndim != 2 or not 1 <= f.shape[1] <= FM_MAX_DIM or f.shape[0] < 1:
+        raise ValueError("features are an [n >= 1, 1 <= dim <= %d] array, got shape %s" % (FM_MAX_DIM, f.shape))
+    return f
+
+
+def _match(pairs, device):
+    """`cslam_feature_match_dev`: per pair (nn01, nn10, mutual rows [m, 2]), int64."""
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    pairs = [(_features(a), _features(b)) for a, b in pairs]
+    n = len(pairs)
+    if n == 0:
+        return []
+    dim = pairs[0][0].shape[1]
+    if any(a.shape[1] != dim or b.shape[1] != dim for a, b in pairs):
+        raise ValueError("all feature arrays of a call need the same dimension")
+    a_off = np.zeros(n + 1, dtype=np.int64)
+    b_off = np.zeros(n + 1, dtype=np.int64)
+    a_off[1:] = np.cumsum([len(a) for a, _ in pairs])
+    b_off[1:] = np.cumsum([len(b) for _, b in pairs])
+    na, nb = int(a_off[-1]), int(b_off[-1])
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_a = torch.from_numpy(np.concatenate([a for a, _ in pairs], axis=0)).to(dev)
+        t_b = torch.from_numpy(np.concatenate([b for _, b in pairs], axis=0)).to(dev)
+        t_ao = torch.from_numpy(a_off).to(dev)
+        t_bo = torch.from_numpy(b_off).to(dev)
+        t_out = torch.empty(3 * na + nb + n, dtype=torch.int32, device=dev)     # nn01 | nn10 | pairs | counts: one download
+        base = t_out.data_ptr()
+        _lib.check(lib.cslam_feature_match_dev(t_a.data_ptr(), t_ao.data_ptr(), t_b.data_ptr(), t_bo.data_ptr(), n, dim, base,
+                                               base + 4 * na, base + 4 * (na + nb), base + 4 * (3 * na + nb), _host(a_off),
+                                               _host(b_off), _stream()))
+        out = t_out.cpu().numpy().astype(np.int64)
+    rows = out[na + nb:3 * na + nb].reshape(na, 2)
+    return [(out[a_off[p]:a_off[p + 1]], out[na + b_off[p]:na + b_off[p + 1]],
+             rows[a_off[p]:a_off[p] + out[3 * na + nb + p]]) for p in range(n)]
+
+
+def find_knn(feat0, feat1, device=0):
+    """For every row of feat0 the nearest row of feat1 in squared Euclidean distance, ties -> the lower row (the
+    reference's `find_knn_cpu` with knn=1, icp_utils.py:40-46), brute force on the GPU."""
+    return _match([(feat0, feat1)], device)[0][0]
+
+
+def find_correspondences_pairs(pairs, mutual_filter=True, device=0):
+    """`find_correspondences` for a list of (feats0, feats1) in ONE call: per pair (idx0, idx1)."""
+    out = []
+    for nn01, _, rows in _match(pairs, device):
+        out.append((rows[:, 0].copy(), rows[:, 1].copy()) if mutual_filter else (np.arange(len(nn01)), nn01))
+    return out
+
+
+def find_correspondences(feats0, feats1, mutual_filter=True, device=0):
+    """Counterpart of the reference's `find_correspondences` (icp_utils.py:49-65): rows (idx0[k], idx1[k]) are each
+    other's nearest neighbour in feature space; without the filter every row of feats0 with its nearest in feats1."""
+    return find_correspondences_pairs([(feats0, feats1)], mutual_filter, device)[0]
 
 
 def _register(pairs, inits, max_dists, max_iters, relative_fitness, relative_rmse, want_correspondences, device):

@@ -416,6 +416,60 @@ int cslam_voxel_downsample_dev(const double *d_points, const int64_t *d_offsets,
                                double *d_out, int64_t *d_out_offsets, int32_t *d_counts, int32_t *d_status,
                                const int64_t *h_offsets, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Lidar loop closures: FPFH features and mutual nearest neighbours in feature space, the inputs of a robust fit
+ * (cslam/lidar_pr/icp_utils.py:26-65: `extract_fpfh`, `find_knn_cpu`, `find_correspondences`).  The robust fit itself
+ * (TEASER++, icp_utils.py:68-83,116-121) is not part of this library.  Float64 throughout, nothing contracted, no
+ * float atomics, every sum in one fixed order: a cloud's (a pair's) result does not depend on the rest of the batch.
+ * The rules follow open3d's EstimateNormals.cpp and Feature.cpp in structure and fix what those leave to a KD-tree, a
+ * hash map or an eigen-solver; parity with open3d itself is not pinned (as for the ICP above).
+ * Clouds are batched as for cslam_voxel_downsample_dev: d_points [total, 3], cloud c owns rows d_offsets[c] ..
+ * d_offsets[c+1]-1 (int64, n_clouds + 1 entries from 0, empty clouds allowed); h_offsets is a host copy of the offsets
+ * or NULL (then they are read back once: the call's only host wait).  Neighbour indices are cloud-local int32.
+ * CSLAM_E_INVALID, before anything touches HIP: a radius that is not finite or <= 0, max_nn < 1 (or > 256 for the
+ * search), a list width outside [1, 256], dim outside [1, 64], n_clouds / n_pairs outside [1, 65535], NULL arguments,
+ * host offsets that do not start at 0, that decrease, or (matching) that leave a feature array without a row.
+ *
+ * cslam_knn_radius_dev -- the hybrid search of open3d's KDTreeSearchParamHybrid(radius, max_nn) (icp_utils.py:29-30,
+ *   35-36), brute force.  The list of point i is i itself first (d^2 = 0), then the other points j of its cloud with
+ *   d^2 = fma(dz, dz, fma(dy, dy, dx * dx)) <= radius^2 in ascending (d^2, j), cut to max_nn entries in all; points
+ *   that coincide with i are ordinary neighbours at d^2 = 0.  d_idx [total, max_nn] (-1 beyond the count), d_d2
+ *   [total, max_nn] (+infinity beyond the count), d_count [total].  Any density is handled: the on-chip candidate buffer
+ *   is cut to its best max_nn - 1 whenever it fills. */
+int cslam_knn_radius_dev(const double *d_points, const int64_t *d_offsets, int n_clouds, double radius, int max_nn,
+                         int32_t *d_idx, double *d_d2, int32_t *d_count, const int64_t *h_offsets, void *stream);
+/* cslam_normals_dev -- open3d's estimate_normals (icp_utils.py:28-30) from neighbour lists of width list_width.  It uses
+ *   the first min(max_nn, entries with d^2 <= radius^2) entries of a list, i.e. exactly the list of a search at
+ *   (radius, max_nn) when the given lists come from a search at least as wide.  With fewer than 3 entries the normal is
+ *   (0, 0, 1).  Otherwise: coordinates relative to the query point, their mean in list order, the 3 x 3 covariance of the
+ *   centred values in list order divided by the count, and the unit eigenvector of its smallest eigenvalue (cyclic Jacobi).
+ *   Sign -- the one deliberate deviation from open3d, which leaves it to its eigen-solver: n . (viewpoint - p) >= 0, and
+ *   where that product is exactly 0 the component of largest magnitude is positive.  viewpoint: host [3], NULL = the
+ *   origin (keyframe clouds are in the sensor frame).  d_normals [total, 3]. */
+int cslam_normals_dev(const double *d_points, const int64_t *d_offsets, int n_clouds, const int32_t *d_idx,
+                      const double *d_d2, const int32_t *d_count, int list_width, double radius, int max_nn,
+                      const double *viewpoint, double *d_normals, const int64_t *h_offsets, void *stream);
+/* cslam_fpfh_dev -- open3d's compute_fpfh_feature (icp_utils.py:32-37) from points, normals and neighbour lists.
+ *   Pair features are open3d's ComputePairFeatures, with its swap when acos|n1.d| > acos|n2.d| and the zero vector for
+ *   coinciding points or a vanishing cross product; bins floor(11 (f0 + pi) / (2 pi)), floor(11 (f1 + 1) / 2),
+ *   floor(11 (f2 + 1) / 2), each clamped to [0, 10].  An SPFH bin is an integer count times 100 / (k - 1), k the list's
+ *   count (0 when k <= 1).  FPFH of point i: for the list entries 1 .. k-1 in order with d^2 != 0, acc[j] +=
+ *   spfh[j, idx] / d^2 (the weight is the squared distance, as in open3d); s_g = the sum of acc over group g's 11 bins in
+ *   ascending j; result acc[j] * (100 / s_g) + spfh[j, i], without the scaling where s_g == 0.
+ *   d_fpfh [total, 33]; d_spfh: NULL (the library's scratch is used) or [total, 33], the SPFH. */
+int cslam_fpfh_dev(const double *d_points, const double *d_normals, const int64_t *d_offsets, int n_clouds,
+                   const int32_t *d_idx, const double *d_d2, const int32_t *d_count, int list_width, double *d_fpfh,
+                   double *d_spfh, const int64_t *h_offsets, void *stream);
+/* cslam_feature_match_dev -- find_knn_cpu in both directions and the mutual filter of find_correspondences
+ *   (icp_utils.py:40-65) for n_pairs pairs of feature arrays: d_a [total_a, dim], d_b [total_b, dim], offsets as above
+ *   with at least one row per array.  d_nn01[i] = argmin over the rows j of the pair's b of sum_d (a_d - b_d)^2,
+ *   accumulated in ascending d, ties -> the lower j (pair-local index); d_nn10 likewise from b to a.  Brute force.
+ *   d_pairs / d_pair_count: both NULL, or [total_a, 2] and [n_pairs]: pair p's rows (i, nn01[i]) with nn10[nn01[i]] == i
+ *   in ascending i, written from row d_a_off[p] on, and their number. */
+int cslam_feature_match_dev(const double *d_a, const int64_t *d_a_off, const double *d_b, const int64_t *d_b_off,
+                            int n_pairs, int dim, int32_t *d_nn01, int32_t *d_nn10, int32_t *d_pairs,
+                            int32_t *d_pair_count, const int64_t *h_a_off, const int64_t *h_b_off, void *stream);
+
 /* Winograd F(2x2, 3x3) transforms for the 3x3 / stride 1 / pad 1 convolutions of the extractor backbone
  * (the VGG-16 trunk built at cslam/vpr/netvlad.py:163-171; the reference runs it through torch's direct
  * convolution).  Activations are NHWC float32.  conv(x, g) + bias = output(bmm(input(x), U)) with

@@ -121,6 +121,11 @@ _SIGNATURES = {
     "cslam_normals_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp]),
     "cslam_fpfh_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp]),
     "cslam_feature_match_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_robust_graph_dev": (_i, [_vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_robust_clique_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_robust_rotation_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_robust_translation_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp]),
+    "cslam_robust_fit_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_wino4_fused_c64_h_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_h_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_r_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),

@@ -1,16 +1,21 @@
 #!/usr/bin/env python
-"""Relative transform between two lidar keyframes on an MI355X: batched point-to-point ICP, and the FPFH features and
-mutual matches a robust coarse fit starts from.
+"""Relative transform between two lidar keyframes on an MI355X: FPFH features, mutual matches, the robust coarse fit
+and batched point-to-point ICP.
 
 Counterpart of cslam/lidar_pr/icp_utils.py (`compute_transform`, called by lidar_handler_node.py:115,133 for every
 accepted ScanContext match).  The reference runs FPFH + mutual nearest neighbours + TEASER++ for a coarse alignment and
-then open3d's `registration_icp(src, dst, voxel_size, T, PointToPoint, max_iteration=100)` (icp_utils.py:126-134).
-Here the refinement keeps open3d's documented semantics exactly, and the coarse alignment comes from what this library
-already computes: the yaw shift of the ScanContext match (`ScanContextMatching.last_yaw_diff_deg`), helped by two
-coarse ICP stages at a larger correspondence radius (`DEFAULT_STAGES`).  `extract_fpfh` and `find_correspondences`
-(icp_utils.py:26-65) have counterparts of the same names here (csrc/fpfh.hip, batched forms `extract_fpfh_clouds` and
-`find_correspondences_pairs`): they produce putative correspondences that do not come from the alignment under test.
-TEASER++, the robust fit that would consume them, has no counterpart yet, and `compute_transform` does not use them.
+then open3d's `registration_icp(src, dst, voxel_size, T, PointToPoint, max_iteration=100)` (icp_utils.py:126-134), and
+accepts the match when TEASER's maximum clique has more than min_inliers members.  Both coarse alignments exist here:
+  coarse="yaw" (the default of `compute_transform` / `solve_icp`): the yaw shift of the ScanContext match
+      (`ScanContextMatching.last_yaw_diff_deg`), helped by two coarse ICP stages at a larger correspondence radius
+      (`DEFAULT_STAGES`); accepted on a correspondence count and a fitness;
+  coarse="teaser" (`solve_teaser`, `solve_teaser_pairs`): the reference's path.  `extract_fpfh` and `find_correspondences`
+      (icp_utils.py:26-65; csrc/fpfh.hip, batched forms `extract_fpfh_clouds` and `find_correspondences_pairs`) give
+      putative matches that do not come from the alignment under test, and the robust fit (csrc/robust.hip: `robust_fit_pairs`,
+      staged `consistency_graph`, `max_clique`, `robust_rotation`, `robust_translation`) is TEASER++'s algorithm at the
+      reference's parameters: the consistency graph of the matches, its exact maximum clique, GNC-TLS for the rotation and
+      per-axis TLS for the translation.  It needs no yaw, and its acceptance test is the reference's: the clique size.
+The refinement keeps open3d's documented semantics exactly in both.
 
 The loop is hand-written HIP (csrc/icp.hip behind `cslam_icp_register_dev`): float64, brute-force nearest neighbours,
 fixed summation order -- a pair's result is the same bits alone or in any batch.  There is no CPU path: without the
@@ -49,6 +54,11 @@ FM_CHUNK = 32         # target rows per LDS chunk of the feature matching kernel
 FM_MAX_LANES = 16     # chunk lanes of its grid: a target of more chunks than this is walked lane-strided
 FM_MAX_DIM = 64       # widest feature
 FPFH_BINS = 33
+ROBUST_MAX_N = 8192            # most correspondences of a pair the robust fit attempts (csrc/robust.hip); above it: status 2
+ROBUST_GRAPH_BLOCK = 64        # rows of the consistency graph per workgroup
+ROBUST_GRAPH_CHUNK = 256       # matched points per LDS chunk of the graph kernel; the tests size around it
+ROBUST_STACK_DEPTH = 512       # deepest branch of the clique search below a root; deeper ends the search uncertified
+ROBUST_DEFAULT_NODE_BUDGET = 2097152     # nodes of one pair's clique search (CSLAM_ROBUST_DEFAULT_NODE_BUDGET)
 
 
 def Rt2T(R, t):
@@ -416,6 +426,356 @@ def find_correspondences(feats0, feats1, mutual_filter=True, device=0):
     return find_correspondences_pairs([(feats0, feats1)], mutual_filter, device)[0]
 
 
+# ---- the robust coarse fit (csrc/robust.hip) ------------------------------------------------------------------------
+def _matched(pairs):
+    """Matched points of a list of pairs: (ms [total, 3], md [total, 3], offsets).  A pair is (src_points, dst_points)
+    with row k of one matched to row k of the other."""
+    ms, md = [], []
+    for a, b in pairs:
+        a = np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(-1, 3))
+        b = np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1, 3))
+        if a.shape != b.shape:
+            raise ValueError("matched points come in pairs: %s source rows, %s target rows" % (a.shape, b.shape))
+        ms.append(a)
+        md.append(b)
+    off = np.zeros(len(pairs) + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(a) for a in ms])
+    cat = lambda xs: np.concatenate(xs, axis=0) if xs else np.zeros((0, 3))
+    return cat(ms), cat(md), off
+
+
+def _noise(noise_bound):
+    c = float(noise_bound)
+    if not (np.isfinite(c) and c > 0):
+        raise _lib.CslamHipError("invalid argument: noise_bound must be positive and finite")
+    return c
+
+
+def _budget(node_budget):
+    b = int(node_budget)
+    if b < 1:
+        raise _lib.CslamHipError("invalid argument: node_budget must be at least 1")
+    return b
+
+
+def _used(off):
+    """The correspondences the stages use per pair (0 above the cap) and the word offsets of the bit matrices."""
+    n = np.diff(off)
+    n = np.where(n > ROBUST_MAX_N, 0, n)
+    words = np.zeros(len(off), dtype=np.int64)
+    words[1:] = np.cumsum(n * ((n + 63) // 64))
+    return n, words
+
+
+def _dev(arr, dev):
+    import torch
+    a = np.ascontiguousarray(arr)
+    return torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(dev)
+
+
+def consistency_graph_pairs(pairs, noise_bound, device=0):
+    """The consistency graphs of a list of (matched source points, matched target points) in ONE call
+    (`cslam_robust_graph_dev`): per pair (adj [N, ceil(N / 64)] uint64, deg [N] int32).  Matches i and j are joined iff
+    the distance between the two source points and that between the two target points differ by 2 noise_bound at most.
+    Bit j of row i is bit j % 64 of word j // 64.  A pair of more than ROBUST_MAX_N rows gets an empty result."""
+    c = _noise(noise_bound)
+    ms, md, off = _matched(pairs)
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    n, words = _used(off)
+    if len(pairs) == 0:
+        return []
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_ms, t_md, t_off = _dev(ms, dev), _dev(md, dev), _dev(off, dev)
+        t_adj = torch.zeros(max(int(words[-1]), 1), dtype=torch.int64, device=dev)
+        t_adj_off = torch.zeros(len(off), dtype=torch.int64, device=dev)
+        t_deg = torch.zeros(max(int(off[-1]), 1), dtype=torch.int32, device=dev)
+        _lib.check(lib.cslam_robust_graph_dev(t_ms.data_ptr(), t_md.data_ptr(), t_off.data_ptr(), None, len(pairs), c, t_adj.data_ptr(),
+                                              t_adj_off.data_ptr(), t_deg.data_ptr(), _host(off), None, _stream()))
+        adj, deg, adj_off = t_adj.cpu().numpy().view(np.uint64), t_deg.cpu().numpy(), t_adj_off.cpu().numpy()
+    assert np.array_equal(adj_off, words)
+    return [(adj[words[p]:words[p + 1]].reshape(int(n[p]), -1).copy() if n[p] else np.zeros((0, 0), np.uint64),
+             deg[off[p]:off[p] + n[p]].copy()) for p in range(len(pairs))]
+
+
+def consistency_graph(src_points, dst_points, noise_bound, device=0):
+    return consistency_graph_pairs([(src_points, dst_points)], noise_bound, device)[0]
+
+
+def max_clique_graphs(graphs, node_budget=ROBUST_DEFAULT_NODE_BUDGET, device=0):
+    """The maximum cliques of a list of bit matrices (as `consistency_graph` returns them) in ONE call
+    (`cslam_robust_clique_dev`): per graph (clique: ascending int64 indices, certified, nodes).  The search is exact;
+    `certified` is False when `node_budget` nodes did not finish it (or a branch went deeper than ROBUST_STACK_DEPTH below
+    its root): the clique is then the best found, never smaller than the greedy one.  Of equal cliques the greedy one wins,
+    then the first that the search of the lowest root in the (core number, index) order meets."""
+    budget = _budget(node_budget)
+    graphs = [np.ascontiguousarray(g, dtype=np.uint64) for g in graphs]
+    for g in graphs:
+        if g.ndim != 2 or g.shape[1] != (g.shape[0] + 63) // 64 or g.shape[0] > ROBUST_MAX_N:
+            raise ValueError("a graph is an [N <= %d, ceil(N / 64)] uint64 bit matrix, got shape %s" % (ROBUST_MAX_N, g.shape))
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    if not graphs:
+        return []
+    npairs = len(graphs)
+    off = np.zeros(npairs + 1, dtype=np.int64)
+    off[1:] = np.cumsum([len(g) for g in graphs])
+    n, words = _used(off)
+    adj = np.concatenate([g.reshape(-1) for g in graphs]) if words[-1] else np.zeros(1, np.uint64)
+    deg = np.concatenate([np.unpackbits(g.view(np.uint8).reshape(len(g), 8 * g.shape[1]), axis=1).sum(axis=1, dtype=np.int32) for g in graphs])
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_adj, t_words, t_deg, t_off = _dev(adj.view(np.int64), dev), _dev(words, dev), _dev(deg.astype(np.int32), dev), _dev(off, dev)
+        t_clique = torch.zeros(max(int(off[-1]), 1), dtype=torch.int32, device=dev)
+        t_small = torch.zeros((2, npairs), dtype=torch.int32, device=dev)
+        t_nodes = torch.zeros(npairs, dtype=torch.int64, device=dev)
+        _lib.check(lib.cslam_robust_clique_dev(t_adj.data_ptr(), t_words.data_ptr(), t_deg.data_ptr(), t_off.data_ptr(), None, npairs, budget,
+                                               t_clique.data_ptr(), t_small[0].data_ptr(), t_small[1].data_ptr(), t_nodes.data_ptr(),
+                                               _host(off), None, _stream()))
+        clique, small, nodes = t_clique.cpu().numpy(), t_small.cpu().numpy(), t_nodes.cpu().numpy()
+    return [(clique[off[p]:off[p] + small[0, p]].astype(np.int64), bool(small[1, p]), int(nodes[p])) for p in range(npairs)]
+
+
+def max_clique(graph, node_budget=ROBUST_DEFAULT_NODE_BUDGET, return_info=False, device=0):
+    """The maximum clique of one bit matrix: ascending indices; with `return_info` (clique, certified, nodes)."""
+    out = max_clique_graphs([graph], node_budget, device)[0]
+    return out if return_info else out[0]
+
+
+def _index_lists(cliques, off):
+    """Per-pair index lists in the capacity layout (None = all rows in order): (int32 [total], sizes int32 [n])."""
+    total = int(off[-1])
+    flat = np.zeros(max(total, 1), dtype=np.int32)
+    sizes = np.zeros(len(off) - 1, dtype=np.int32)
+    for p in range(len(off) - 1):
+        cap = int(off[p + 1] - off[p])
+        q = np.arange(cap) if cliques is None or cliques[p] is None else np.asarray(cliques[p], dtype=np.int64).reshape(-1)
+        if len(q) > cap or (len(q) and (q.min() < 0 or q.max() >= cap)):
+            raise ValueError("an index list addresses rows outside its pair")
+        flat[off[p]:off[p] + len(q)] = q
+        sizes[p] = len(q)
+    return flat, sizes
+
+
+def robust_rotation_pairs(pairs, noise_bound, cliques=None, device=0):
+    """GNC-TLS rotations of a list of (matched source points, matched target points) in ONE call
+    (`cslam_robust_rotation_dev`), each on the chain of its index list (`cliques[p]`, None = every row in order): per pair
+    (R [3, 3], weights [K - 1], iterations)."""
+    c = _noise(noise_bound)
+    ms, md, off = _matched(pairs)
+    flat, sizes = _index_lists(cliques, off)
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    if not pairs:
+        return []
+    npairs = len(pairs)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_ms, t_md, t_off, t_q, t_k = _dev(ms, dev), _dev(md, dev), _dev(off, dev), _dev(flat, dev), _dev(sizes, dev)
+        t_R = torch.zeros((npairs, 9), dtype=torch.float64, device=dev)
+        t_w = torch.zeros(len(flat), dtype=torch.float64, device=dev)
+        t_it = torch.zeros(npairs, dtype=torch.int32, device=dev)
+        _lib.check(lib.cslam_robust_rotation_dev(t_ms.data_ptr(), t_md.data_ptr(), t_off.data_ptr(), t_q.data_ptr(), t_k.data_ptr(), npairs,
+                                                 c, t_R.data_ptr(), t_w.data_ptr(), t_it.data_ptr(), _host(off), _stream()))
+        R, w, it = t_R.cpu().numpy(), t_w.cpu().numpy(), t_it.cpu().numpy()
+    return [(R[p].reshape(3, 3).copy(), w[off[p]:off[p] + max(int(sizes[p]) - 1, 0)].copy(), int(it[p])) for p in range(npairs)]
+
+
+def robust_rotation(src_points, dst_points, noise_bound, clique=None, device=0):
+    return robust_rotation_pairs([(src_points, dst_points)], noise_bound, [clique], device)[0]
+
+
+def robust_translation_pairs(pairs, rotations, noise_bound, cliques=None, device=0):
+    """Per-axis TLS translations of a list of (matched source points, matched target points) under the given rotations in
+    ONE call (`cslam_robust_translation_dev`): per pair (t [3], sets [3, K] bool: the consensus set of each axis)."""
+    c = _noise(noise_bound)
+    ms, md, off = _matched(pairs)
+    flat, sizes = _index_lists(cliques, off)
+    if len(rotations) != len(pairs):
+        raise ValueError("%d rotations for %d pairs" % (len(rotations), len(pairs)))
+    R = np.stack([np.asarray(r, dtype=np.float64).reshape(9) for r in rotations]) if pairs else np.zeros((0, 9))
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    if not pairs:
+        return []
+    npairs, total = len(pairs), max(int(off[-1]), 1)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_ms, t_md, t_off, t_q, t_k, t_R = (_dev(x, dev) for x in (ms, md, off, flat, sizes, R))
+        t_t = torch.zeros((npairs, 3), dtype=torch.float64, device=dev)
+        t_set = torch.zeros((3, total), dtype=torch.int32, device=dev)
+        _lib.check(lib.cslam_robust_translation_dev(t_ms.data_ptr(), t_md.data_ptr(), t_off.data_ptr(), t_q.data_ptr(), t_k.data_ptr(),
+                                                    t_R.data_ptr(), npairs, c, t_t.data_ptr(), t_set.data_ptr() if off[-1] else None,
+                                                    _host(off), _stream()))
+        t, sets = t_t.cpu().numpy(), t_set.cpu().numpy()
+    return [(t[p].copy(), sets[:, off[p]:off[p] + sizes[p]].astype(bool)) for p in range(npairs)]
+
+
+def robust_translation(src_points, dst_points, rotation, noise_bound, clique=None, device=0):
+    return robust_translation_pairs([(src_points, dst_points)], [rotation], noise_bound, [clique], device)[0]
+
+
+class RobustFit:
+    """The robust fit of one pair: `transformation` (4 x 4, source -> target), `status` (0 solved; 1 fewer than 3 clique
+    members: the identity, never a fit; 2 more than ROBUST_MAX_N correspondences: not attempted), `clique` (ascending
+    correspondence indices), `clique_size`, `iterations` of the rotation, `certified`, `nodes` of the clique search and
+    `correspondences` given."""
+
+    def __init__(self, transformation, status, clique, clique_size, iterations, certified, nodes, correspondences):
+        self.transformation = transformation
+        self.status = status
+        self.clique = clique
+        self.clique_size = clique_size
+        self.iterations = iterations
+        self.certified = certified
+        self.nodes = nodes
+        self.correspondences = correspondences
+
+    def __repr__(self):
+        return "RobustFit(status=%d, clique_size=%d of %d, iterations=%d, certified=%s, nodes=%d)" % (
+            self.status, self.clique_size, self.correspondences, self.iterations, self.certified, self.nodes)
+
+
+def _fit_enqueue(lib, p_src, p_src_off, p_dst, p_dst_off, p_rows, p_row_off, p_count, n, c, budget, row_off, h_count, dev):
+    """`cslam_robust_fit_dev` on device pointers: device (T [n, 16], info [n, 6], clique [total rows])."""
+    import torch
+    t_T = torch.zeros((n, 16), dtype=torch.float64, device=dev)
+    t_info = torch.zeros((n, 6), dtype=torch.int64, device=dev)
+    t_clique = torch.zeros(max(int(row_off[-1]), 1), dtype=torch.int32, device=dev)
+    _lib.check(lib.cslam_robust_fit_dev(p_src, p_src_off, p_dst, p_dst_off, p_rows, p_row_off, p_count, n, c, budget, t_T.data_ptr(),
+                                        t_info.data_ptr(), t_clique.data_ptr(), _host(row_off),
+                                        _host(h_count) if h_count is not None else None, _stream()))
+    return t_T, t_info, t_clique
+
+
+def _fits(T, info, clique, row_off):
+    return [RobustFit(T[p].reshape(4, 4).copy(), int(info[p, 0]), clique[row_off[p]:row_off[p] + info[p, 1]].astype(np.int64),
+                      int(info[p, 1]), int(info[p, 2]), bool(info[p, 3]), int(info[p, 4]), int(info[p, 5])) for p in range(len(T))]
+
+
+def robust_fit_pairs(pairs, noise_bound, node_budget=ROBUST_DEFAULT_NODE_BUDGET, device=0):
+    """The robust fit (consistency graph, maximum clique, GNC-TLS rotation, per-axis TLS translation: TEASER++ with the
+    reference's parameters, icp_utils.py:68-83,116-121) for a list of pairs in ONE batched call (`cslam_robust_fit_dev`).
+    A pair is (matched source points, matched target points), or (source cloud, target cloud, rows) with rows [N, 2] =
+    (source row, target row) as `find_correspondences` gives them.  Returns one `RobustFit` per pair."""
+    c, budget = _noise(noise_bound), _budget(node_budget)
+    srcs, dsts, rows = [], [], []
+    for pr in pairs:
+        a, b = _rows(pr[0]), _rows(pr[1])
+        if len(pr) == 2:
+            if a.shape != b.shape:
+                raise ValueError("matched points come in pairs: %s source rows, %s target rows" % (a.shape, b.shape))
+            r = np.repeat(np.arange(len(a), dtype=np.int32)[:, None], 2, axis=1)
+        else:
+            r = np.asarray(pr[2])
+            r = (np.stack(r, axis=1) if isinstance(pr[2], tuple) else r).astype(np.int32).reshape(-1, 2)
+        srcs.append(a)
+        dsts.append(b)
+        rows.append(r)
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    n = len(srcs)
+    if n == 0:
+        return []
+    cum = lambda xs: np.concatenate([[0], np.cumsum([len(x) for x in xs])]).astype(np.int64)
+    s_off, d_off, r_off = cum(srcs), cum(dsts), cum(rows)
+    count = np.diff(r_off).astype(np.int32)
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_src, t_dst = _dev(np.concatenate(srcs), dev), _dev(np.concatenate(dsts), dev)
+        t_rows = _dev(np.concatenate(rows), dev)
+        t_so, t_do, t_ro, t_cnt = _dev(s_off, dev), _dev(d_off, dev), _dev(r_off, dev), _dev(count, dev)
+        t_T, t_info, t_clique = _fit_enqueue(lib, t_src.data_ptr(), t_so.data_ptr(), t_dst.data_ptr(), t_do.data_ptr(), t_rows.data_ptr(),
+                                             t_ro.data_ptr(), t_cnt.data_ptr(), n, c, budget, r_off, count, dev)
+        T, info, clique = t_T.cpu().numpy(), t_info.cpu().numpy(), t_clique.cpu().numpy()
+    return _fits(T, info, clique, r_off)
+
+
+class TeaserSuccess(Success):
+    """The success flag of `solve_teaser` / `compute_transform(coarse="teaser")`: truthy iff the maximum clique has MORE
+    members than min_inliers (the reference's test, icp_utils.py:136).  Besides the ICP figures of `Success` it carries
+    `clique_size`, `certified`, `status`, `matches` (the mutual matches the fit started from) and `coarse`, the 4 x 4 of
+    the robust fit before the refinement."""
+
+    def __init__(self, ok, result, fit):
+        Success.__init__(self, ok, result)
+        self.clique_size = fit.clique_size
+        self.certified = fit.certified
+        self.status = fit.status
+        self.matches = fit.correspondences
+        self.clique = fit.clique
+        self.nodes = fit.nodes
+        self.coarse = fit.transformation
+
+    def __repr__(self):
+        return "TeaserSuccess(%s, clique_size=%d of %d matches, certified=%s, fitness=%.4f, inlier_rmse=%.4f)" % (
+            self.ok, self.clique_size, self.matches, self.certified, self.fitness, self.inlier_rmse)
+
+
+def solve_teaser_pairs(pairs, voxel_size, min_inliers, node_budget=ROBUST_DEFAULT_NODE_BUDGET, device=0):
+    """The reference's `solve_teaser` (icp_utils.py:103-139) for a list of (src, dst) pairs in ONE batched chain on the
+    device: one upload, FPFH of all 2n clouds, mutual matches, the robust fit with noise_bound = voxel_size, and
+    `registration_icp(voxel_size, 100 iterations)` from the fit's transforms.  Returns per pair (valid, translation,
+    rotation) with dst ~ rotation . src + translation; `valid` is a `TeaserSuccess`: clique size > min_inliers.  A pair
+    that is not valid returns the unrefined fit, as the reference does."""
+    c, budget = _noise(voxel_size), _budget(node_budget)
+    pairs = list(pairs)
+    srcs = [_points(s) for s, _ in pairs]
+    dsts = [_points(d) for _, d in pairs]
+    if any(len(x) == 0 for x in srcs + dsts):
+        raise ValueError("every cloud needs at least one point with finite coordinates")
+    _lib.require_gpu()
+    lib = _lib.load()
+    import torch
+    n = len(pairs)
+    if n == 0:
+        return []
+    dev = torch.device("cuda", device)
+    with torch.cuda.device(dev):
+        t_in, off, head = _upload_clouds(srcs + dsts, dev)               # the sources, then the targets
+        lists = _knn_enqueue(lib, t_in, off, head, 5.0 * c, 100)
+        t_n = _normals_enqueue(lib, t_in, off, head, lists, 2.0 * c, 30, (0.0, 0.0, 0.0))
+        t_f = _fpfh_enqueue(lib, t_in, off, head, t_n, lists, False)
+        a_off = off[:n + 1].copy()
+        b_off = (off[n:] - off[n]).copy()
+        na, nb = int(a_off[-1]), int(b_off[-1])
+        t_bo = torch.from_numpy(b_off).to(dev)
+        p_src, p_so = t_in.data_ptr() + head, t_in.data_ptr()
+        p_dst, p_do = p_src + 24 * na, t_bo.data_ptr()
+        t_m = torch.empty(3 * na + nb + n, dtype=torch.int32, device=dev)     # nn01 | nn10 | rows | counts
+        p_rows, p_cnt = t_m.data_ptr() + 4 * (na + nb), t_m.data_ptr() + 4 * (3 * na + nb)
+        _lib.check(lib.cslam_feature_match_dev(t_f.data_ptr(), p_so, t_f.data_ptr() + 8 * FPFH_BINS * na, p_do, n, FPFH_BINS, t_m.data_ptr(),
+                                               t_m.data_ptr() + 4 * na, p_rows, p_cnt, _host(a_off), _host(b_off), _stream()))
+        t_T, t_info, t_clique = _fit_enqueue(lib, p_src, p_so, p_dst, p_do, p_rows, p_so, p_cnt, n, c, budget, a_off, None, dev)
+        t_ref = torch.empty((n, 16), dtype=torch.float64, device=dev)
+        t_stats = torch.empty((n, 4), dtype=torch.float64, device=dev)
+        dists, iters = np.array([c]), np.array([100], dtype=np.int32)
+        _lib.check(lib.cslam_icp_register_dev(p_src, p_so, p_dst, p_do, n, t_T.data_ptr(), _host(dists), _host(iters), 1, 1e-6, 1e-6,
+                                              t_ref.data_ptr(), t_stats.data_ptr(), _stream()))
+        out = torch.cat((t_T, t_ref, t_stats, t_info.to(torch.float64)), dim=1).cpu().numpy()     # one copy of the results
+        clique = t_clique.cpu().numpy()
+    fits = _fits(out[:, :16], out[:, 36:42].astype(np.int64), clique, a_off)
+    results = []
+    for p, fit in enumerate(fits):
+        valid = fit.status == 0 and fit.clique_size > min_inliers
+        T = out[p, 16:32].reshape(4, 4).copy() if valid else fit.transformation
+        icp = RegistrationResult(T, float(out[p, 32]), float(out[p, 33]), int(out[p, 34]), int(out[p, 35]))
+        results.append((TeaserSuccess(valid, icp, fit), T[:3, 3].copy(), T[:3, :3].copy()))
+    return results
+
+
+def solve_teaser(src, dst, voxel_size, min_inliers, node_budget=ROBUST_DEFAULT_NODE_BUDGET, device=0):
+    """Counterpart of the reference's solve_teaser (icp_utils.py:103-139), same name and argument order: (valid,
+    translation, rotation)."""
+    return solve_teaser_pairs([(src, dst)], voxel_size, min_inliers, node_budget, device)[0]
+
+
 def _register(pairs, inits, max_dists, max_iters, relative_fitness, relative_rmse, want_correspondences, device):
     _lib.require_gpu()
     lib = _lib.load()
@@ -531,14 +891,23 @@ def _accept(result, min_inliers, min_fitness):
     return result.correspondences > min_inliers and result.fitness >= min_fitness
 
 
-def solve_icp(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0):
+def _coarse(coarse):
+    if coarse not in ("yaw", "teaser"):
+        raise ValueError("coarse is 'yaw' or 'teaser', got %r" % (coarse,))
+    return coarse
+
+
+def solve_icp(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0, coarse="yaw"):
     """Counterpart of the reference's solve_teaser (icp_utils.py:103-139): (valid, translation, rotation) with
-    dst ~ rotation . src + translation."""
+    dst ~ rotation . src + translation.  coarse="teaser": `solve_teaser` itself (`init_yaw_deg` and `min_fitness` are
+    not used)."""
+    if _coarse(coarse) == "teaser":
+        return solve_teaser(src, dst, voxel_size, min_inliers)
     r = register_pairs([(src, dst)], voxel_size, init_yaw_deg)[0]
     return _accept(r, min_inliers, min_fitness), r.transformation[:3, 3].copy(), r.transformation[:3, :3].copy()
 
 
-def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0):
+def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0, coarse="yaw"):
     """Computes a 3D transform between 2 point clouds (reference icp_utils.py:178-196), dst ~ R . src + t, as
     registration_icp(source=src, target=dst) gives it.
 
@@ -548,6 +917,9 @@ def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_
         min_inliers (int): the registration succeeds with MORE correspondences than this in the final stage ...
         init_yaw_deg: `ScanContextMatching.last_yaw_diff_deg` of the match (None: start from the identity)
         min_fitness: ... and a final fitness (correspondences / source points) of at least this
+        coarse: "yaw" (the default: the staged ICP from the ScanContext yaw, as described above) or "teaser": the
+            reference's own path, `solve_teaser` -- FPFH, mutual matches, the robust fit, one ICP stage; `init_yaw_deg`
+            and `min_fitness` are not used, and the success flag is the reference's: clique size > min_inliers
 
     Returns:
         (Transform, Success): the transform message and a success flag that is truthy / falsy like the reference's bool
@@ -556,8 +928,12 @@ def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_
     A correspondence count is a MUCH weaker test than the size of TEASER++'s maximum clique, which the reference
     compares with min_inliers: the clique certifies mutually consistent matches, a count only says how many source points
     have some target point within voxel_size.  A wrong alignment of two clouds that share a ground plane still has a
-    fitness of about 0.6 (thousands of "inliers"), a right one is above 0.9 on the same clouds.  Set `min_fitness`.
+    fitness of about 0.6 (thousands of "inliers"), a right one is above 0.9 on the same clouds.  Set `min_fitness`, or
+    use coarse="teaser", whose test is the clique itself.
     """
+    if _coarse(coarse) == "teaser":
+        valid, t, R = solve_teaser(src, dst, voxel_size, min_inliers)
+        return to_transform_msg(t, R), valid
     r = register_pairs([(src, dst)], voxel_size, init_yaw_deg)[0]
     transform = to_transform_msg(r.transformation[:3, 3], r.transformation[:3, :3])
     return transform, Success(_accept(r, min_inliers, min_fitness), r)

@@ -418,8 +418,8 @@ int cslam_voxel_downsample_dev(const double *d_points, const int64_t *d_offsets,
 
 /* ------------------------------------------------------------------------------------------------
  * Lidar loop closures: FPFH features and mutual nearest neighbours in feature space, the inputs of a robust fit
- * (cslam/lidar_pr/icp_utils.py:26-65: `extract_fpfh`, `find_knn_cpu`, `find_correspondences`).  The robust fit itself
- * (TEASER++, icp_utils.py:68-83,116-121) is not part of this library.  Float64 throughout, nothing contracted, no
+ * (cslam/lidar_pr/icp_utils.py:26-65: `extract_fpfh`, `find_knn_cpu`, `find_correspondences`).  The robust fit that consumes
+ * them (TEASER++, icp_utils.py:68-83,116-121) is csrc/robust.hip, declared after these.  Float64 throughout, nothing contracted, no
  * float atomics, every sum in one fixed order: a cloud's (a pair's) result does not depend on the rest of the batch.
  * The rules follow open3d's EstimateNormals.cpp and Feature.cpp in structure and fix what those leave to a KD-tree, a
  * hash map or an eigen-solver; parity with open3d itself is not pinned (as for the ICP above).
@@ -469,6 +469,90 @@ int cslam_fpfh_dev(const double *d_points, const double *d_normals, const int64_
 int cslam_feature_match_dev(const double *d_a, const int64_t *d_a_off, const double *d_b, const int64_t *d_b_off,
                             int n_pairs, int dim, int32_t *d_nn01, int32_t *d_nn10, int32_t *d_pairs,
                             int32_t *d_pair_count, const int64_t *h_a_off, const int64_t *h_b_off, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Lidar loop closures: the robust coarse fit from the mutual matches (csrc/robust.hip), the TEASER++ step of
+ * `solve_teaser` (cslam/lidar_pr/icp_utils.py:116-121) with the parameters of `get_teaser_solver` (icp_utils.py:68-83):
+ * cbar2 = 1, no scale estimation, exact maximum clique, CHAIN graph for the rotation, GNC-TLS with factor 1.4, at most
+ * 10000 iterations and cost threshold 1e-16.  Neither TEASER++ nor its source is available where this is built, so parity
+ * with TEASER++ itself is not pinned (as for open3d above); the kernels implement the rules written here.  Float64
+ * throughout, nothing contracted (but the 4 x 4 eigen-solve shared with the ICP, csrc/horn.h, which is compiled as it is
+ * there), no float atomics, every floating sum in one order that depends on the pair's own sizes only: a pair's bytes are
+ * the same alone, in any batch and on any run.  c = noise_bound below.
+ * The staged entries take the MATCHED points: d_ms / d_md [total, 3], row k of pair p's arrays is the k-th matched source /
+ * target point; pair p owns rows d_off[p] .. d_off[p+1]-1 (int64, n_pairs + 1 entries from 0: its capacity) and uses the
+ * first d_count[p] of them (int32; d_count NULL = all).  That is the layout cslam_feature_match_dev writes (rows from
+ * d_a_off[p] on, d_pair_count[p]).  N = the count; a pair with N > CSLAM_ROBUST_MAX_N is not attempted (it is treated as
+ * N = 0 by the stages and gets status 2 from the chained call) and the other pairs are not affected.  Per-pair int32 /
+ * float64 arrays "in the capacity layout" have `total` entries and pair p's begin at d_off[p].
+ * h_off / h_count: host copies, or NULL; when one that is needed to plan the launch is missing, offsets and counts are
+ * read back once (the only host wait of a call).  CSLAM_E_INVALID, before anything touches HIP: n_pairs outside
+ * [1, 65535], a noise bound that is not finite or <= 0, a node budget < 1, NULL arguments, host offsets that do not start
+ * at 0 or that decrease, host counts that are negative or beyond the capacity.  Scratch is the library's own, per
+ * (device, stream). */
+#define CSLAM_ROBUST_MAX_N 8192
+#define CSLAM_ROBUST_DEFAULT_NODE_BUDGET 2097152
+/* cslam_robust_graph_dev -- the consistency graph of TEASER's translation-invariant measurements (the pairwise test of
+ *   its inlier selection, icp_utils.py:116-118 `solver.solve`): for i < j, a = sqrt(fma(dz, dz, fma(dy, dy, dx * dx))) of
+ *   the two matched source points, b the same of the target points; an edge iff |b - a| <= 2 c (equality is an edge).
+ *   d_adj: the N x N bit matrices, pair p's at word d_adj_off[p] (written here, n_pairs + 1 entries: sum of N * W words,
+ *   W = ceil(N / 64)), row i = W 64-bit words, bit j of a row = word j / 64, bit j % 64; symmetric, zero diagonal, the
+ *   padding bits zero.  d_deg: the degrees, capacity layout.  Nothing is stored per pair of matches. */
+int cslam_robust_graph_dev(const double *d_ms, const double *d_md, const int64_t *d_off, const int32_t *d_count, int n_pairs,
+                           double noise_bound, uint64_t *d_adj, int64_t *d_adj_off, int32_t *d_deg, const int64_t *h_off,
+                           const int32_t *h_count, void *stream);
+/* cslam_robust_clique_dev -- the exact maximum clique (TEASER's inlier selection, icp_utils.py:116-118; its size is what
+ *   solve_teaser compares with min_inliers, icp_utils.py:136).  Core numbers by peeling; vertices ordered by ascending
+ *   (core number, index); the GREEDY clique: the vertex of largest core number (the lowest index of equals), then again
+ *   and again the common neighbour of those taken with the largest core number (the lowest index of equals).  Then branch
+ *   and bound on bitsets, one root vertex per wave: root r looks for the largest clique of r and vertices after it in the
+ *   order that beats the greedy one; at a node with clique R and candidates P (taken in ascending order position) the
+ *   candidates are coloured greedily and only those of a colour above (best so far of this root, at least the greedy size)
+ *   - |R| are branched on.  WHICH CLIQUE WINS: the greedy clique unless a larger one exists; otherwise the largest, and of
+ *   equal ones the first that the search of the lowest root in the order meets.  A root's search uses nothing that other
+ *   roots find (their sizes only skip whole roots that cannot hold a clique of the largest size), so the result does not
+ *   depend on timing whenever the search completes.  node_budget: nodes (colourings) of one pair's search in all; when it
+ *   runs out, or a branch gets deeper than 512 below its root, the pair returns the best clique found (never smaller than
+ *   the greedy one) and certified = 0; a search that completes sets certified = 1.
+ *   d_clique: ascending correspondence indices, capacity layout; d_clique_size, d_certified [n_pairs]; d_nodes: NULL or
+ *   [n_pairs], the nodes used. */
+int cslam_robust_clique_dev(const uint64_t *d_adj, const int64_t *d_adj_off, const int32_t *d_deg, const int64_t *d_off,
+                            const int32_t *d_count, int n_pairs, int64_t node_budget, int32_t *d_clique, int32_t *d_clique_size,
+                            int32_t *d_certified, int64_t *d_nodes, const int64_t *h_off, const int32_t *h_count, void *stream);
+/* cslam_robust_rotation_dev -- GNC-TLS on the chain of an index list q[0 .. K-1] (d_clique / d_clique_size, as above)
+ *   (TEASER's rotation solver, icp_utils.py:75-80,116-118): a_k = ms[q[k+1]] - ms[q[k]], b_k likewise on the targets,
+ *   nb2 = 4 c^2 (1e-2 if that is below 1e-16).  w = 1, mu = 1, prev = +inf; for it = 0 .. 9999:
+ *   R = argmax sum w_k b_k . (R a_k) over proper rotations (Horn's quaternion form, no centring); r2_k = |b_k - R a_k|^2;
+ *   at it == 0: mu = 1 / (2 max r2 / nb2 - 1), stop if mu <= 0; th1 = (mu + 1) / mu nb2, th2 = mu / (mu + 1) nb2,
+ *   cost = sum w_k r2_k (old weights); w_k = 0 if r2_k >= th1, 1 if r2_k <= th2, else sqrt(nb2 mu (mu + 1) / r2_k) - mu;
+ *   d = |cost - prev|, mu *= 1.4, prev = cost, stop if d < 1e-16.  One launch, one workgroup per pair, no host wait.
+ *   d_R [n_pairs, 9] row-major; d_weights: the K - 1 final weights, capacity layout; d_iters [n_pairs]: the weight updates
+ *   made (0 when the loop stops at mu <= 0).  K < 2: the identity and 0. */
+int cslam_robust_rotation_dev(const double *d_ms, const double *d_md, const int64_t *d_off, const int32_t *d_clique,
+                              const int32_t *d_clique_size, int n_pairs, double noise_bound, double *d_R, double *d_weights,
+                              int32_t *d_iters, const int64_t *h_off, void *stream);
+/* cslam_robust_translation_dev -- per-axis TLS (TEASER's translation solver, icp_utils.py:116-121): per axis
+ *   x_k = md[q[k]][axis] - ((R0 sx + R1 sy) + R2 sz) with the axis' row of d_R and s = ms[q[k]]; the 2K endpoints x_k -+ c
+ *   in ascending (value, index), the 2K - 1 centres midway between consecutive ones; per centre the consensus set
+ *   |x_k - centre| <= c, the estimate = its mean (summed in index order), the cost sum_set (x_k - estimate)^2 + c (K - |set|);
+ *   a centre with an empty set is left out; the estimate of the lowest cost, ties -> the lower centre.
+ *   d_t [n_pairs, 3]; d_set: NULL or [3, total] int32, 1 for the members of the winning set (axis-major, capacity layout). */
+int cslam_robust_translation_dev(const double *d_ms, const double *d_md, const int64_t *d_off, const int32_t *d_clique,
+                                 const int32_t *d_clique_size, const double *d_R, int n_pairs, double noise_bound, double *d_t,
+                                 int32_t *d_set, const int64_t *h_off, void *stream);
+/* cslam_robust_fit_dev -- the chain (icp_utils.py:116-121) from clouds and correspondence rows: d_src / d_dst and their
+ *   offsets as for cslam_icp_register_dev, d_rows [total, 2] int32 (source row, target row; pair-local) with d_row_off /
+ *   d_count exactly as cslam_feature_match_dev writes d_pairs / d_pair_count with d_a_off.  A row that points outside its
+ *   clouds is consistent with nothing.  Everything runs on the device; the counts are read back once to plan the scratch
+ *   unless h_row_off and h_count are given.
+ *   d_T [n_pairs, 16]: source -> target.  d_info [n_pairs, 6] int64: status, clique size, rotation iterations, certified,
+ *   nodes of the clique search, N.  status 0: solved; 1: fewer than 3 clique members -- the transform is the identity and
+ *   there is never a fit (TEASER's own answer there is arbitrary); 2: N above CSLAM_ROBUST_MAX_N, not attempted.
+ *   d_clique: NULL, or the clique in the capacity layout. */
+int cslam_robust_fit_dev(const double *d_src, const int64_t *d_src_off, const double *d_dst, const int64_t *d_dst_off,
+                         const int32_t *d_rows, const int64_t *d_row_off, const int32_t *d_count, int n_pairs, double noise_bound,
+                         int64_t node_budget, double *d_T, int64_t *d_info, int32_t *d_clique, const int64_t *h_row_off,
+                         const int32_t *h_count, void *stream);
 
 /* Winograd F(2x2, 3x3) transforms for the 3x3 / stride 1 / pad 1 convolutions of the extractor backbone
  * (the VGG-16 trunk built at cslam/vpr/netvlad.py:163-171; the reference runs it through torch's direct

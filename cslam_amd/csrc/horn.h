@@ -1,10 +1,28 @@
 // horn.h -- the rigid fit without scale shared by icp.hip (every ICP update) and robust.hip (the rotation of the robust fit).
+//
+// Accuracy.  icp_rigid_from_sums forms the covariance from UNCENTRED sums, (sum q p^T - sum q . mean p) / n, which loses
+// (|mean| / spread)^2 of the float64 precision.  It is therefore fed coordinates relative to an origin near the clouds:
+// icp.hip takes its sums relative to icp_sum_origin(first target point of the pair) and calls icp_rigid_from_shifted_sums,
+// which fits the shifted sets and moves the translation back.  With that the moved points are within a few ulp of the
+// largest input coordinate of the centred extended-precision fit for clouds of lidar size (a few hundred metres) anywhere
+// float64 represents them to the millimetre (tested to 2^20 m); robust.hip passes differences of points and zero means,
+// which no origin enters.
 #pragma once
+
+// The origin of a pair's sums: its first target point rounded to the multiples of ICP_ORIGIN_GRID per axis.  It depends on
+// the pair alone (so do the sums: alone or in any batch, the same bits), it is exact in float64, and it is zero for a
+// cloud that starts within half a grid step of the frame origin: sensor-frame clouds are summed as they are.
+#define ICP_ORIGIN_GRID 1024.0
+__host__ __device__ static void icp_sum_origin(const double *q0, double *o) {
+    for (int a = 0; a < 3; ++a) o[a] = ICP_ORIGIN_GRID * rint(q0[a] / ICP_ORIGIN_GRID);
+}
 
 // Rigid update without scale from the 17 sums: U (3 x 4, row-major) with q ~ R p + t in the least-squares sense.
 // Horn's closed form: the unit quaternion of R is the eigenvector of the largest eigenvalue of the symmetric 4 x 4
-// N(M), M = sum (p - mean p)(q - mean q)^T.  A zero M (one correspondence) leaves the Jacobi basis at the identity and
-// the first largest eigenvalue picks q = (1, 0, 0, 0): R = I, as the SVD form gives.
+// N(M), M = sum (p - mean p)(q - mean q)^T.  A zero M leaves the Jacobi basis at the identity and the first largest
+// eigenvalue picks q = (1, 0, 0, 0): R = I, as the SVD form gives.  The M of ONE correspondence is zero only where the
+// difference below is not contracted: the device build fuses it, keeps the rounding error of q p and turns that noise into
+// a rotation.  icp_rigid_from_shifted_sums therefore answers one correspondence itself.
 __host__ __device__ static void icp_rigid_from_sums(const double *s, double *U) {
     const double n = s[0];
     double mp[3], mq[3], M[3][3];
@@ -69,4 +87,19 @@ __host__ __device__ static void icp_rigid_from_sums(const double *s, double *U) 
         for (int b = 0; b < 3; ++b) U[4 * a + b] = R[a][b];
         U[4 * a + 3] = mq[a] - (R[a][0] * mp[0] + R[a][1] * mp[1] + R[a][2] * mp[2]);
     }
+}
+
+// The same from sums of (p - o) and (q - o): the fit of the shifted sets is U' = (R, t'), and q ~ R p + t' + o - R o.
+// One correspondence: R = I exactly and t = q - p.
+__host__ __device__ static void icp_rigid_from_shifted_sums(const double *s, const double *o, double *U) {
+    if (s[0] == 1.0) {
+        for (int a = 0; a < 3; ++a) {
+            for (int b = 0; b < 3; ++b) U[4 * a + b] = a == b ? 1.0 : 0.0;
+            U[4 * a + 3] = s[4 + a] - s[1 + a];
+        }
+        return;
+    }
+    icp_rigid_from_sums(s, U);
+    if (o[0] == 0.0 && o[1] == 0.0 && o[2] == 0.0) return;
+    for (int a = 0; a < 3; ++a) U[4 * a + 3] += o[a] - (U[4 * a] * o[0] + U[4 * a + 1] * o[1] + U[4 * a + 2] * o[2]);
 }

@@ -11,12 +11,18 @@
 //                      grid = (source blocks, target chunk lanes, pairs) so that one pair fills the device.
 //                      Output: a partial (d^2, index) per source point and chunk lane.
 //   icp_merge_kernel : minimum over the chunk lanes, ties -> lower target index (argmin); a correspondence is kept
-//                      iff d^2 <= r^2; n, sum p, sum q, sum q p^T, sum d^2 per block by a fixed shuffle tree.
+//                      iff d^2 <= r^2; n, sum p, sum q, sum q p^T, sum d^2 per block by a fixed shuffle tree, p and q
+//                      taken relative to the pair's origin (horn.h icp_sum_origin: its first target point rounded to
+//                      a 1024 m grid, zero for a cloud around the frame origin).
 //   icp_solve_kernel : one wave per pair: block partials added in block order, fitness = n / |src|,
 //                      inlier_rmse = sqrt(sum d^2 / n), open3d's stopping rule, else the rigid update without scale
 //                      (Horn's quaternion form of the Umeyama solution: largest eigenvector of a symmetric 4 x 4 by
 //                      cyclic Jacobi -- a proper rotation by construction, which is what the det = -1 fix of the SVD
-//                      form restores) and T <- U . T.
+//                      form restores) of the shifted sets, the translation moved back to the frame, and T <- U . T.
+// Coordinate range: the uncentred sums lose (distance of the centroid from the sums' origin / spread)^2 of the precision;
+// with the origin at most 512 m per axis from the first target point that leaves the moved points within a few ulp of the
+// largest coordinate of the centred fit, wherever the clouds lie (map-frame, UTM or ENU coordinates included; tested up
+// to 2^20 m).  What remains is the rounding of T . p itself: one ulp of the coordinates per round.
 // No float atomics: every sum has one order that depends on the pair's own sizes only, so a pair's result is the same
 // bits alone or in any batch.  A per-pair `done` flag in device memory turns the kernels of later rounds into
 // immediate returns; the host enqueues max_iteration + 1 rounds per stage without waiting.
@@ -127,16 +133,17 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_merge_kernel(const double *__re
 #pragma unroll
     for (int k = 0; k < ICP_NSUM; ++k) v[k] = 0.0;
     if (keep) {
-        double pt[3];
+        double pt[3], o[3];
         icp_load_point(src, T, p, row, pt);
+        icp_sum_origin(dst + 3 * d0, o);
         const double *q = dst + 3 * (d0 + bi);
         v[0] = 1.0;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { v[1 + a] = pt[a]; v[4 + a] = q[a]; }
+        for (int a = 0; a < 3; ++a) { v[1 + a] = pt[a] - o[a]; v[4 + a] = q[a] - o[a]; }
 #pragma unroll
         for (int b = 0; b < 3; ++b)
 #pragma unroll
-            for (int a = 0; a < 3; ++a) v[7 + 3 * b + a] = __dmul_rn(q[b], pt[a]);
+            for (int a = 0; a < 3; ++a) v[7 + 3 * b + a] = __dmul_rn(v[4 + b], v[1 + a]);
         v[16] = best;
     }
 #pragma unroll
@@ -155,7 +162,8 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_merge_kernel(const double *__re
 
 // open3d's loop (RegistrationICP): evaluate at init; for i = 1 .. max_iteration: update, re-evaluate, stop when both
 // |delta fitness| < relative_fitness and |delta inlier_rmse| < relative_rmse.  Round r is the evaluation after r updates.
-__global__ __launch_bounds__(64) void icp_solve_kernel(const int64_t *__restrict__ src_off, const double *__restrict__ bsums,
+__global__ __launch_bounds__(64) void icp_solve_kernel(const int64_t *__restrict__ src_off, const double *__restrict__ dst,
+                                                      const int64_t *__restrict__ dst_off, const double *__restrict__ bsums,
                                                       int max_blocks, int round, int max_iter, double rel_fitness,
                                                       double rel_rmse, double *__restrict__ T, double *__restrict__ stats,
                                                       int *__restrict__ done) {
@@ -182,8 +190,9 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(const int64_t *__restrict
         return;
     }
     if (n <= 0.0) return;                                  // no correspondences: the update is the identity
-    double U[12], Tn[12];
-    icp_rigid_from_sums(s, U);
+    double U[12], Tn[12], o[3];
+    icp_sum_origin(dst + 3 * dst_off[p], o);
+    icp_rigid_from_shifted_sums(s, o, U);
     double *Tp = T + 16 * (int64_t)p;
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 4; ++b)
@@ -312,8 +321,8 @@ CSLAM_API int cslam_icp_register_dev(const double *d_src, const int64_t *d_src_o
         for (int round = 0; round <= max_iter[s]; ++round) {
             icp_launch_eval(d_src, d_src_off, d_dst, d_dst_off, n_pairs, sh, ws, d_T_out, ws.done, r2, nullptr, nullptr, ws.bsums,
                             st);
-            hipLaunchKernelGGL(icp_solve_kernel, dim3((unsigned)n_pairs), dim3(64), 0, st, d_src_off, ws.bsums, sh.src_blocks,
-                               round, max_iter[s], rel_fitness, rel_rmse, d_T_out, d_stats_out, ws.done);
+            hipLaunchKernelGGL(icp_solve_kernel, dim3((unsigned)n_pairs), dim3(64), 0, st, d_src_off, d_dst, d_dst_off, ws.bsums,
+                               sh.src_blocks, round, max_iter[s], rel_fitness, rel_rmse, d_T_out, d_stats_out, ws.done);
         }
     }
     HIP_TRY(hipGetLastError());

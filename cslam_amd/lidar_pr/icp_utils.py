@@ -871,6 +871,18 @@ def registration_icp(src, dst, max_correspondence_distance, init=np.eye(4), max_
                      relative_rmse, True, device)[0]
 
 
+def registration_icp_pairs(pairs, max_correspondence_distance, inits=None, max_iteration=100, relative_fitness=1e-6,
+                           relative_rmse=1e-6, device=0):
+    """`registration_icp` for a list of (src, dst) pairs in ONE batched call: one radius and one iteration cap for all,
+    `inits` one 4 x 4 per pair (None = the identity for all).  A pair's result is the same bits as alone."""
+    pairs = list(pairs)
+    inits = [np.eye(4)] * len(pairs) if inits is None else list(inits)
+    if len(inits) != len(pairs):
+        raise ValueError("inits has %d entries for %d pairs" % (len(inits), len(pairs)))
+    return _register(pairs, inits, [max_correspondence_distance], [max_iteration], relative_fitness, relative_rmse, True,
+                     device)
+
+
 def register_pairs(pairs, voxel_size, init_yaw_deg=None, stages=DEFAULT_STAGES, correspondence_sets=False, device=0):
     """Register a list of (src, dst) pairs in ONE batched call.  `init_yaw_deg`: None, one ScanContext yaw shift for
     all pairs, or one per pair (entries may be None).  Stage s runs open3d's loop with the radius

@@ -374,6 +374,11 @@ int cslam_scancontext_from_cloud_dev(const double *d_points, const int64_t *d_of
  * The offsets are read back once (the only host wait) and every size is checked before anything is launched:
  * CSLAM_E_INVALID on offsets that do not increase, a non-positive or non-finite radius, n_pairs outside [1, 65535].
  * Results do not depend on which other pairs are in the batch (no atomics; every sum has one fixed order).
+ * Coordinate range: the clouds may lie anywhere float64 resolves them (map-frame, UTM or ENU coordinates included).  The sums of
+ * an update are taken relative to the pair's first target point rounded to a 1024 m grid (zero, and so the sums as written,
+ * for clouds around the frame origin), the shifted sets are fitted and the translation is moved back: for clouds of lidar
+ * size the moved source points stay within a few ulp of the largest coordinate of an extended-precision centred fit (tested
+ * up to 2^20 m: at most 3 ulp; bound of the tests 256).  One correspondence gives R = I and t = q - p exactly.
  *
  * correspondences: one evaluation at d_T ([n_pairs,16] row-major 4x4, NULL = identity).  d_idx[row] = the nearest
  *   target point of T . src[row] (index within the pair's target cloud), -1 where its squared distance exceeds

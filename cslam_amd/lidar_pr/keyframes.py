@@ -9,9 +9,8 @@ back in one copy.  There is no CPU path: without the library or a GPU `CslamHipE
 """
 import numpy as np
 
-from .. import _lib
-from . import icp_utils
-from .scancontext import theta_360_error
+from . import scancontext, voxel
+from ._batch import gpu, rows, upload
 
 RINGS, SECTORS, MAX_LENGTH = 20, 60, 80       # as ScanContext (the ScanContext paper's shape)
 
@@ -22,25 +21,19 @@ def ingest(clouds, voxel_size, device=0):
     descriptors: [len(clouds), RINGS * SECTORS] float64, the rows `ScanContext.compute_embeddings` gives for the same
     clouds; a point at exactly 360 degrees raises the same IndexError.
     downsampled: the list `icp_utils.downsample_clouds(clouds, voxel_size)` gives (`VoxelSizeError` likewise)."""
-    _lib.require_gpu()
-    lib = _lib.load()
-    import torch
-    clouds = [icp_utils._rows(c) for c in clouds]
-    n = len(clouds)
-    if n == 0:
-        return np.zeros((0, RINGS * SECTORS)), []
-    dev = torch.device("cuda", device)
-    desc_bytes = 8 * n * RINGS * SECTORS
-    with torch.cuda.device(dev):
-        t_in, off, head = icp_utils._upload_clouds(clouds, dev)
-        t_out, lay = icp_utils._voxel_enqueue(lib, t_in, off, head, voxel_size, False, extra_bytes=desc_bytes + 256)
+    with gpu(device) as (lib, dev):
+        clouds = [rows(c) for c in clouds]
+        n = len(clouds)
+        if n == 0:
+            return np.zeros((0, RINGS * SECTORS)), []
+        desc_bytes = 8 * n * RINGS * SECTORS
+        cl = upload(clouds, dev)
+        t_out, lay = voxel.enqueue(lib, cl, voxel_size, False, extra_bytes=desc_bytes + 256)
         base = t_out.data_ptr() + lay["extra"]
-        _lib.check(lib.cslam_scancontext_from_cloud_dev(
-            t_in.data_ptr() + head, t_in.data_ptr(), n, RINGS, SECTORS, float(MAX_LENGTH), base, base + desc_bytes,
-            torch.cuda.current_stream().cuda_stream))
+        scancontext.enqueue(lib, cl.rows, cl.d_off, n, RINGS, SECTORS, MAX_LENGTH, base, base + desc_bytes)
         host = t_out.cpu().numpy()
     at = lay["extra"]
     if int(host[at + desc_bytes:at + desc_bytes + 4].view(np.int32)[0]) != 0:
-        raise theta_360_error(SECTORS)
+        raise scancontext.theta_360_error(SECTORS)
     desc = host[at:at + desc_bytes].view(np.float64).reshape(n, RINGS * SECTORS).copy()
-    return desc, icp_utils._voxel_unpack(host, lay, n, False)
+    return desc, voxel.unpack(host, lay, n, False)

@@ -23,6 +23,13 @@ def theta_360_error(sectors):
                       "as in the reference's ptcloud2sc)" % (sectors, sectors))
 
 
+def enqueue(lib, p_points, p_offsets, n, rings, sectors, max_length, p_out, p_status):
+    """`cslam_scancontext_from_cloud_dev` on device pointers, on the current stream (`keyframes.ingest` shares it)."""
+    import torch
+    _lib.check(lib.cslam_scancontext_from_cloud_dev(p_points, p_offsets, n, rings, sectors, float(max_length), p_out, p_status,
+                                                    torch.cuda.current_stream().cuda_stream))
+
+
 class ScanContext:
     """
     Scan Context descriptor for point clouds
@@ -53,10 +60,8 @@ class ScanContext:
         out = torch.empty((len(clouds), self.shape[0] * self.shape[1]), dtype=torch.float64, device=dev)
         status = torch.zeros(1, dtype=torch.int32, device=dev)
         with torch.cuda.device(dev):
-            st = torch.cuda.current_stream().cuda_stream
-            _lib.check(self._lib.cslam_scancontext_from_cloud_dev(
-                pts.data_ptr(), off.data_ptr(), len(clouds), self.shape[0], self.shape[1],
-                float(self.max_length), out.data_ptr(), status.data_ptr(), st))
+            enqueue(self._lib, pts.data_ptr(), off.data_ptr(), len(clouds), self.shape[0], self.shape[1], self.max_length,
+                    out.data_ptr(), status.data_ptr())
         res = out.cpu().numpy()
         if int(status.item()) != 0:
             raise theta_360_error(self.shape[1])

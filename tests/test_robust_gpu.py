@@ -219,6 +219,30 @@ def test_unrelated_scenes_are_not_valid(street):
     assert np.array_equal(iref.Rt2T(R, t), valid.coarse)             # the unrefined fit, as the reference returns it
 
 
+def test_solve_teaser_pairs_equals_its_stages_bit_for_bit(u, street):
+    """The chain on one upload and raw device pointers against the four public stages it is made of, each with its own
+    upload and download: the same bits in every field, for the related pairs and for the unrelated one."""
+    scenes, pairs, results = street
+    for (src, dst), (valid, t, R) in zip(pairs, results):
+        f0, f1 = u.extract_fpfh_clouds([src, dst], V)
+        rows = u.find_correspondences(f0, f1)
+        fit = u.robust_fit_pairs([(src, dst, rows)], V)[0]
+        icp = u.registration_icp_pairs([(src, dst)], V, inits=[fit.transformation])[0]
+        assert valid.coarse.tobytes() == fit.transformation.tobytes()
+        assert np.array_equal(valid.clique, fit.clique) and valid.clique.dtype == fit.clique.dtype
+        assert (valid.clique_size, valid.matches, valid.status, valid.certified) == (fit.clique_size, len(rows[0]), fit.status,
+                                                                                      fit.certified)
+        assert valid.matches == fit.correspondences
+        if valid:
+            assert valid.transformation.tobytes() == icp.transformation.tobytes()
+            assert (valid.fitness, valid.inlier_rmse, valid.correspondences, valid.iterations) == (
+                icp.fitness, icp.inlier_rmse, icp.correspondences, icp.iterations)
+        else:
+            assert valid.transformation.tobytes() == fit.transformation.tobytes()        # the unrefined fit
+        assert np.array_equal(iref.Rt2T(R, t), valid.transformation)
+    assert [bool(v) for v, _, _ in results] == [True] * len(E2E_SEEDS) + [False]
+
+
 def test_compute_transform_by_teaser_needs_no_yaw(u, street):
     scenes, pairs, results = street
     src, dst = pairs[0]

@@ -52,6 +52,7 @@ def main():
     import icp_reference as ref
     from cslam_amd import _lib
     from cslam_amd.lidar_pr import icp_utils as u
+    from cslam_amd.lidar_pr._batch import upload
 
     _lib.require_gpu()
     lib = _lib.load()
@@ -66,9 +67,9 @@ def main():
           f"matching block {u.FM_BLOCK} x chunk {u.FM_CHUNK}")
 
     for name, sel in (("1 cloud", clouds[:1]), (f"{args.batch} clouds", clouds)):
-        t_in, off, head = u._upload_clouds(sel, dev)
-        n, total = len(sel), int(off[-1])
-        pts, d_off = t_in.data_ptr() + head, t_in.data_ptr()
+        cl = upload(sel, dev)
+        n, total, off = len(sel), int(cl.off[-1]), cl.off
+        pts, d_off = cl.rows, cl.d_off
         idx = torch.empty((total, 100), dtype=torch.int32, device=dev)
         d2 = torch.empty((total, 100), dtype=torch.float64, device=dev)
         cnt = torch.empty(total, dtype=torch.int32, device=dev)

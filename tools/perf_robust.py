@@ -45,8 +45,9 @@ class Staged:
     def __init__(self, torch, lib, u, pairs, c, budget):
         self.torch, self.lib, self.c, self.budget, self.n = torch, lib, c, budget, len(pairs)
         dev = torch.device("cuda", 0)
-        ms, md, self.off = u._matched(pairs)
-        used, words = u._used(self.off)
+        from cslam_amd.lidar_pr import robust
+        ms, md, self.off = robust.matched_points(pairs)
+        used, words = robust.used(self.off)
         self.h_off = self.off.ctypes.data_as(C.c_void_p)
         self.t_ms, self.t_md, self.t_off = (torch.from_numpy(x).to(dev) for x in (ms, md, self.off))
         total = int(self.off[-1])

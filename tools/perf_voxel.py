@@ -48,6 +48,7 @@ def main():
     import icp_reference as ref
     from cslam_amd import _lib
     from cslam_amd.lidar_pr import icp_utils
+    from cslam_amd.lidar_pr._batch import upload
 
     _lib.require_gpu()
     lib = _lib.load()
@@ -60,16 +61,16 @@ def main():
 
     def device_call(sel):
         clouds = [scans[k] for k in sel]
-        t_in, off, head = icp_utils._upload_clouds(clouds, dev)
-        n, total = len(clouds), int(off[-1])
+        cl = upload(clouds, dev)
+        n, total = len(clouds), int(cl.off[-1])
         out = torch.empty((total, 3), dtype=torch.float64, device=dev)
         out_off = torch.empty(n + 1, dtype=torch.int64, device=dev)
         status = torch.empty(n, dtype=torch.int32, device=dev)
 
         def run():
-            _lib.check(lib.cslam_voxel_downsample_dev(t_in.data_ptr() + head, t_in.data_ptr(), n, voxel, out.data_ptr(),
+            _lib.check(lib.cslam_voxel_downsample_dev(cl.rows, cl.d_off, n, voxel, out.data_ptr(),
                                                       out_off.data_ptr(), None, status.data_ptr(),
-                                                      off.ctypes.data_as(C.c_void_p), st))
+                                                      cl.off.ctypes.data_as(C.c_void_p), st))
         return run, out, out_off, total
 
     for name, sel in (("1 scan", [0]), (f"{args.batch} scans", list(range(args.batch)))):

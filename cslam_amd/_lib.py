@@ -116,6 +116,7 @@ _SIGNATURES = {
     "cslam_scancontext_from_cloud_dev": (_i, [_vp, _vp, _i, _i, _i, C.c_double, _vp, _vp, _vp]),
     "cslam_icp_correspondences_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, C.c_double, _vp, _vp, _vp]),
     "cslam_icp_register_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "cslam_icp_register_plane_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp]),
     "cslam_voxel_downsample_dev": (_i, [_vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_knn_radius_dev": (_i, [_vp, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp, _vp]),
     "cslam_normals_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _i, C.c_double, _i, _vp, _vp, _vp, _vp]),

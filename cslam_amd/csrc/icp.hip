@@ -1,4 +1,4 @@
-// icp.hip -- batched point-to-point ICP for lidar loop closures (gfx950).
+// icp.hip -- batched ICP for lidar loop closures (gfx950): point-to-point, and point-to-plane as a compile-time form.
 //
 // Replaces the refinement step of cslam/lidar_pr/icp_utils.py:126-134 (open3d `registration_icp` with
 // TransformationEstimationPointToPoint and ICPConvergenceCriteria(max_iteration=100)) for a batch of
@@ -19,6 +19,10 @@
 //                      (Horn's quaternion form of the Umeyama solution: largest eigenvector of a symmetric 4 x 4 by
 //                      cyclic Jacobi -- a proper rotation by construction, which is what the det = -1 fix of the SVD
 //                      form restores) of the shifted sets, the translation moved back to the frame, and T <- U . T.
+// Point-to-plane (cslam_icp_register_plane_dev; open3d's TransformationEstimationPointToPlane) differs in the update only:
+// icp_merge_kernel<true> sums the 29 terms of plane.h (n, d^2, J J^T, J r with J = [(p - o) x n, n], n the target's normal at
+// q) through the same tree, icp_solve_kernel<true> solves the 6 x 6 (lane 0; identity for a singular system) and composes
+// as above.  The <false> instantiations are the point-to-point kernels, instruction for instruction.
 // Coordinate range: the uncentred sums lose (distance of the centroid from the sums' origin / spread)^2 of the precision;
 // with the origin at most 512 m per axis from the first target point that leaves the moved points within a few ulp of the
 // largest coordinate of the centred fit, wherever the clouds lie (map-frame, UTM or ENU coordinates included; tested up
@@ -28,6 +32,7 @@
 // immediate returns; the host enqueues max_iteration + 1 rounds per stage without waiting.
 #include "common.h"
 #include "horn.h"
+#include "plane.h"
 
 #define ICP_BLOCK 256        // source points per workgroup (4 waves)
 #define ICP_CHUNK 1024       // target points per LDS chunk: 24 KiB, 6 workgroups per CU
@@ -96,14 +101,19 @@ __device__ __forceinline__ double icp_wave_sum(double v) {
     return v;
 }
 
+// PLANE: the 29 sums of plane.h (dst_nrm: the targets' normals, rows as dst) in place of the 17 of the rigid fit; a
+// compile-time choice, so that the point-to-point kernel is the code it was.
+template <bool PLANE>
 __global__ __launch_bounds__(ICP_BLOCK) void icp_merge_kernel(const double *__restrict__ src, const int64_t *__restrict__ src_off,
                                                              const double *__restrict__ dst, const int64_t *__restrict__ dst_off,
                                                              const double *__restrict__ T, const int *__restrict__ done,
                                                              int64_t total_src, int lanes, const double *__restrict__ part_d2,
                                                              const int *__restrict__ part_idx, double r2,
                                                              int *__restrict__ corr_idx, double *__restrict__ corr_d2,
-                                                             double *__restrict__ bsums, int max_blocks) {
-    __shared__ double s_w[ICP_BLOCK / 64][ICP_NSUM];
+                                                             double *__restrict__ bsums, int max_blocks,
+                                                             const double *__restrict__ dst_nrm) {
+    constexpr int NSUM = PLANE ? ICP_PLANE_NSUM : ICP_NSUM;
+    __shared__ double s_w[ICP_BLOCK / 64][NSUM];
     const int p = blockIdx.y, t = threadIdx.x;
     if (done && done[p]) return;
     const int64_t s0 = src_off[p], ns = src_off[p + 1] - s0;
@@ -129,59 +139,69 @@ __global__ __launch_bounds__(ICP_BLOCK) void icp_merge_kernel(const double *__re
         corr_d2[row] = best;
     }
     if (!bsums) return;
-    double v[ICP_NSUM];
+    double v[NSUM];
 #pragma unroll
-    for (int k = 0; k < ICP_NSUM; ++k) v[k] = 0.0;
+    for (int k = 0; k < NSUM; ++k) v[k] = 0.0;
     if (keep) {
         double pt[3], o[3];
         icp_load_point(src, T, p, row, pt);
         icp_sum_origin(dst + 3 * d0, o);
         const double *q = dst + 3 * (d0 + bi);
-        v[0] = 1.0;
+        if constexpr (PLANE) {
+            const double *nq = dst_nrm + 3 * (d0 + bi);
+            const double ps[3] = {pt[0] - o[0], pt[1] - o[1], pt[2] - o[2]}, dq[3] = {pt[0] - q[0], pt[1] - q[1], pt[2] - q[2]};
+            const double nr[3] = {nq[0], nq[1], nq[2]};
+            icp_plane_terms(ps, dq, nr, best, v);
+        } else {
+            v[0] = 1.0;
 #pragma unroll
-        for (int a = 0; a < 3; ++a) { v[1 + a] = pt[a] - o[a]; v[4 + a] = q[a] - o[a]; }
+            for (int a = 0; a < 3; ++a) { v[1 + a] = pt[a] - o[a]; v[4 + a] = q[a] - o[a]; }
 #pragma unroll
-        for (int b = 0; b < 3; ++b)
+            for (int b = 0; b < 3; ++b)
 #pragma unroll
-            for (int a = 0; a < 3; ++a) v[7 + 3 * b + a] = __dmul_rn(v[4 + b], v[1 + a]);
-        v[16] = best;
+                for (int a = 0; a < 3; ++a) v[7 + 3 * b + a] = __dmul_rn(v[4 + b], v[1 + a]);
+            v[16] = best;
+        }
     }
 #pragma unroll
-    for (int k = 0; k < ICP_NSUM; ++k) {
+    for (int k = 0; k < NSUM; ++k) {
         const double w = icp_wave_sum(v[k]);
         if ((t & 63) == 0) s_w[t >> 6][k] = w;
     }
     __syncthreads();
-    if (t < ICP_NSUM) {
+    if (t < NSUM) {
         double a = s_w[0][t];
 #pragma unroll
         for (int w = 1; w < ICP_BLOCK / 64; ++w) a += s_w[w][t];
-        bsums[((int64_t)p * max_blocks + blockIdx.x) * ICP_NSUM + t] = a;
+        bsums[((int64_t)p * max_blocks + blockIdx.x) * NSUM + t] = a;
     }
 }
 
 // open3d's loop (RegistrationICP): evaluate at init; for i = 1 .. max_iteration: update, re-evaluate, stop when both
 // |delta fitness| < relative_fitness and |delta inlier_rmse| < relative_rmse.  Round r is the evaluation after r updates.
+// PLANE: the 29 sums and the update of plane.h; everything else -- fitness, inlier_rmse, the stopping rule -- is the same.
+template <bool PLANE>
 __global__ __launch_bounds__(64) void icp_solve_kernel(const int64_t *__restrict__ src_off, const double *__restrict__ dst,
                                                       const int64_t *__restrict__ dst_off, const double *__restrict__ bsums,
                                                       int max_blocks, int round, int max_iter, double rel_fitness,
                                                       double rel_rmse, double *__restrict__ T, double *__restrict__ stats,
                                                       int *__restrict__ done) {
-    __shared__ double s[ICP_NSUM];
+    constexpr int NSUM = PLANE ? ICP_PLANE_NSUM : ICP_NSUM, SUM_D2 = PLANE ? 1 : 16;
+    __shared__ double s[NSUM];
     const int p = blockIdx.x, t = threadIdx.x;
     if (done[p]) return;
     const int64_t ns = src_off[p + 1] - src_off[p];
     const int nb = (int)((ns + ICP_BLOCK - 1) / ICP_BLOCK);
-    if (t < ICP_NSUM) {
+    if (t < NSUM) {
         double a = 0.0;
-        for (int b = 0; b < nb; ++b) a += bsums[((int64_t)p * max_blocks + b) * ICP_NSUM + t];
+        for (int b = 0; b < nb; ++b) a += bsums[((int64_t)p * max_blocks + b) * NSUM + t];
         s[t] = a;
     }
     __syncthreads();
     if (t != 0) return;
     const double n = s[0];
     const double fitness = n > 0.0 ? n / (double)ns : 0.0;
-    const double rmse = n > 0.0 ? sqrt(s[16] / n) : 0.0;
+    const double rmse = n > 0.0 ? sqrt(s[SUM_D2] / n) : 0.0;
     double *st = stats + 4 * (int64_t)p;
     const double prev_f = st[0], prev_r = st[1];
     st[0] = fitness; st[1] = rmse; st[2] = n; st[3] = (double)round;
@@ -192,7 +212,11 @@ __global__ __launch_bounds__(64) void icp_solve_kernel(const int64_t *__restrict
     if (n <= 0.0) return;                                  // no correspondences: the update is the identity
     double U[12], Tn[12], o[3];
     icp_sum_origin(dst + 3 * dst_off[p], o);
-    icp_rigid_from_shifted_sums(s, o, U);
+    if constexpr (PLANE) {
+        if (!icp_plane_update_from_shifted_sums(s, o, U)) return;      // a singular system: the update is the identity
+    } else {
+        icp_rigid_from_shifted_sums(s, o, U);
+    }
     double *Tp = T + 16 * (int64_t)p;
     for (int a = 0; a < 3; ++a)
         for (int b = 0; b < 4; ++b)
@@ -242,10 +266,10 @@ struct IcpScratch {
 
 static StreamScratch g_icp_scratch;
 
-static int icp_scratch(const IcpShape &sh, int n_pairs, hipStream_t st, IcpScratch *ws) {
+static int icp_scratch(const IcpShape &sh, int n_pairs, int nsum, hipStream_t st, IcpScratch *ws) {
     const size_t n_part = (size_t)sh.lanes * (size_t)sh.total_src;
     const size_t b_d2 = round_up64((int64_t)(n_part * 8), 256), b_idx = round_up64((int64_t)(n_part * 4), 256);
-    const size_t b_sums = round_up64((int64_t)n_pairs * sh.src_blocks * ICP_NSUM * 8, 256);
+    const size_t b_sums = round_up64((int64_t)n_pairs * sh.src_blocks * nsum * 8, 256);
     const size_t b_done = round_up64((int64_t)n_pairs * 4, 256);
     int dev = 0;
     HIP_TRY(hipGetDevice(&dev));
@@ -264,15 +288,17 @@ static int icp_common_checks(const double *d_src, const int64_t *d_src_off, cons
     return CSLAM_OK;
 }
 
-// one evaluation of every unfinished pair at T: nearest neighbours, then the merge (+ sums when bsums is given)
+// one evaluation of every unfinished pair at T: nearest neighbours, then the merge (+ sums when bsums is given: the 29 of
+// plane.h with the targets' normals, else the 17 of the rigid fit)
 static void icp_launch_eval(const double *d_src, const int64_t *d_src_off, const double *d_dst, const int64_t *d_dst_off,
                             int n_pairs, const IcpShape &sh, const IcpScratch &ws, const double *d_T, const int *d_done,
-                            double r2, int *d_idx, double *d_dist2, double *bsums, hipStream_t st) {
+                            double r2, int *d_idx, double *d_dist2, double *bsums, const double *d_nrm, hipStream_t st) {
     hipLaunchKernelGGL(icp_nn_kernel, dim3((unsigned)sh.src_blocks, (unsigned)sh.lanes, (unsigned)n_pairs), dim3(ICP_BLOCK), 0, st,
                        d_src, d_src_off, d_dst, d_dst_off, d_T, d_done, sh.total_src, ws.part_d2, ws.part_idx);
-    hipLaunchKernelGGL(icp_merge_kernel, dim3((unsigned)sh.src_blocks, (unsigned)n_pairs), dim3(ICP_BLOCK), 0, st, d_src, d_src_off,
-                       d_dst, d_dst_off, d_T, d_done, sh.total_src, sh.lanes, ws.part_d2, ws.part_idx, r2, d_idx, d_dist2, bsums,
-                       sh.src_blocks);
+    auto merge = d_nrm ? icp_merge_kernel<true> : icp_merge_kernel<false>;
+    hipLaunchKernelGGL(merge, dim3((unsigned)sh.src_blocks, (unsigned)n_pairs), dim3(ICP_BLOCK), 0, st, d_src, d_src_off, d_dst,
+                       d_dst_off, d_T, d_done, sh.total_src, sh.lanes, ws.part_d2, ws.part_idx, r2, d_idx, d_dist2, bsums,
+                       sh.src_blocks, d_nrm);
 }
 
 CSLAM_API int cslam_icp_correspondences_dev(const double *d_src, const int64_t *d_src_off, const double *d_dst,
@@ -287,9 +313,43 @@ CSLAM_API int cslam_icp_correspondences_dev(const double *d_src, const int64_t *
     IcpShape sh;
     if ((rc = icp_read_shape(d_src_off, d_dst_off, n_pairs, st, &sh))) return rc;
     IcpScratch ws;
-    if ((rc = icp_scratch(sh, n_pairs, st, &ws))) return rc;
+    if ((rc = icp_scratch(sh, n_pairs, ICP_NSUM, st, &ws))) return rc;
     icp_launch_eval(d_src, d_src_off, d_dst, d_dst_off, n_pairs, sh, ws, d_T, nullptr, max_dist * max_dist, d_idx, d_dist2,
-                    nullptr, st);
+                    nullptr, nullptr, st);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+// both estimators: d_nrm = the targets' normals for point-to-plane, NULL for point-to-point
+static int icp_register(const double *d_src, const int64_t *d_src_off, const double *d_dst, const int64_t *d_dst_off, int n_pairs,
+                        const double *d_init, const double *max_dist, const int *max_iter, int n_stages, double rel_fitness,
+                        double rel_rmse, double *d_T_out, double *d_stats_out, const double *d_nrm, hipStream_t st) {
+    ARG_CHECK(d_T_out && d_stats_out && max_dist && max_iter, "NULL argument");
+    ARG_CHECK(n_stages >= 1 && n_stages <= ICP_MAX_STAGES, "n_stages must be in [1, 16]");
+    for (int s = 0; s < n_stages; ++s) {
+        ARG_CHECK(max_dist[s] > 0.0 && max_dist[s] < INFINITY, "max_dist must be positive and finite");
+        ARG_CHECK(max_iter[s] >= 0 && max_iter[s] <= 100000, "max_iter must be in [0, 100000]");
+    }
+    ARG_CHECK(rel_fitness == rel_fitness && rel_rmse == rel_rmse, "relative_fitness / relative_rmse is NaN");
+    PTR_DEVICE(d_src);
+    int rc;
+    IcpShape sh;
+    if ((rc = icp_read_shape(d_src_off, d_dst_off, n_pairs, st, &sh))) return rc;
+    IcpScratch ws;
+    if ((rc = icp_scratch(sh, n_pairs, d_nrm ? ICP_PLANE_NSUM : ICP_NSUM, st, &ws))) return rc;
+    hipLaunchKernelGGL(icp_init_kernel, dim3((unsigned)ceil_div64(16 * (int64_t)n_pairs, 256)), dim3(256), 0, st, d_init, n_pairs,
+                       d_T_out, d_stats_out);
+    auto solve = d_nrm ? icp_solve_kernel<true> : icp_solve_kernel<false>;
+    for (int s = 0; s < n_stages; ++s) {
+        HIP_TRY(hipMemsetAsync(ws.done, 0, (size_t)n_pairs * sizeof(int), st));
+        const double r2 = max_dist[s] * max_dist[s];
+        for (int round = 0; round <= max_iter[s]; ++round) {
+            icp_launch_eval(d_src, d_src_off, d_dst, d_dst_off, n_pairs, sh, ws, d_T_out, ws.done, r2, nullptr, nullptr, ws.bsums,
+                            d_nrm, st);
+            hipLaunchKernelGGL(solve, dim3((unsigned)n_pairs), dim3(64), 0, st, d_src_off, d_dst, d_dst_off, ws.bsums, sh.src_blocks,
+                               round, max_iter[s], rel_fitness, rel_rmse, d_T_out, d_stats_out, ws.done);
+        }
+    }
     HIP_TRY(hipGetLastError());
     return CSLAM_OK;
 }
@@ -300,31 +360,18 @@ CSLAM_API int cslam_icp_register_dev(const double *d_src, const int64_t *d_src_o
                                      double *d_stats_out, void *stream) {
     int rc = icp_common_checks(d_src, d_src_off, d_dst, d_dst_off, n_pairs);
     if (rc) return rc;
-    ARG_CHECK(d_T_out && d_stats_out && max_dist && max_iter, "NULL argument");
-    ARG_CHECK(n_stages >= 1 && n_stages <= ICP_MAX_STAGES, "n_stages must be in [1, 16]");
-    for (int s = 0; s < n_stages; ++s) {
-        ARG_CHECK(max_dist[s] > 0.0 && max_dist[s] < INFINITY, "max_dist must be positive and finite");
-        ARG_CHECK(max_iter[s] >= 0 && max_iter[s] <= 100000, "max_iter must be in [0, 100000]");
-    }
-    ARG_CHECK(rel_fitness == rel_fitness && rel_rmse == rel_rmse, "relative_fitness / relative_rmse is NaN");
-    PTR_DEVICE(d_src);
-    hipStream_t st = (hipStream_t)stream;
-    IcpShape sh;
-    if ((rc = icp_read_shape(d_src_off, d_dst_off, n_pairs, st, &sh))) return rc;
-    IcpScratch ws;
-    if ((rc = icp_scratch(sh, n_pairs, st, &ws))) return rc;
-    hipLaunchKernelGGL(icp_init_kernel, dim3((unsigned)ceil_div64(16 * (int64_t)n_pairs, 256)), dim3(256), 0, st, d_init, n_pairs,
-                       d_T_out, d_stats_out);
-    for (int s = 0; s < n_stages; ++s) {
-        HIP_TRY(hipMemsetAsync(ws.done, 0, (size_t)n_pairs * sizeof(int), st));
-        const double r2 = max_dist[s] * max_dist[s];
-        for (int round = 0; round <= max_iter[s]; ++round) {
-            icp_launch_eval(d_src, d_src_off, d_dst, d_dst_off, n_pairs, sh, ws, d_T_out, ws.done, r2, nullptr, nullptr, ws.bsums,
-                            st);
-            hipLaunchKernelGGL(icp_solve_kernel, dim3((unsigned)n_pairs), dim3(64), 0, st, d_src_off, d_dst, d_dst_off, ws.bsums,
-                               sh.src_blocks, round, max_iter[s], rel_fitness, rel_rmse, d_T_out, d_stats_out, ws.done);
-        }
-    }
-    HIP_TRY(hipGetLastError());
-    return CSLAM_OK;
+    return icp_register(d_src, d_src_off, d_dst, d_dst_off, n_pairs, d_init, max_dist, max_iter, n_stages, rel_fitness, rel_rmse,
+                        d_T_out, d_stats_out, nullptr, (hipStream_t)stream);
+}
+
+CSLAM_API int cslam_icp_register_plane_dev(const double *d_src, const int64_t *d_src_off, const double *d_dst,
+                                           const int64_t *d_dst_off, const double *d_dst_normals, int n_pairs,
+                                           const double *d_init, const double *max_dist, const int *max_iter, int n_stages,
+                                           double rel_fitness, double rel_rmse, double *d_T_out, double *d_stats_out,
+                                           void *stream) {
+    int rc = icp_common_checks(d_src, d_src_off, d_dst, d_dst_off, n_pairs);
+    if (rc) return rc;
+    ARG_CHECK(d_dst_normals, "d_dst_normals is NULL");
+    return icp_register(d_src, d_src_off, d_dst, d_dst_off, n_pairs, d_init, max_dist, max_iter, n_stages, rel_fitness, rel_rmse,
+                        d_T_out, d_stats_out, d_dst_normals, (hipStream_t)stream);
 }

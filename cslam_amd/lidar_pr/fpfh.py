@@ -55,9 +55,14 @@ def fpfh_enqueue(lib, cl, t_normals, lists, spfh):
 def extract_enqueue(lib, cl, voxel_size, viewpoint):
     """The reference's `extract_fpfh` on uploaded clouds: device [total, 33].  One neighbour search at (5 voxels, 100) serves
     both steps: the normals at (2 voxels, 30) use the prefix of each list, which is the list a search of their own returns."""
+    return extract_with_normals_enqueue(lib, cl, voxel_size, viewpoint)[0]
+
+
+def extract_with_normals_enqueue(lib, cl, voxel_size, viewpoint):
+    """`extract_enqueue` and the normals it computes on the way: device ([total, 33], [total, 3])."""
     lists = knn_enqueue(lib, cl, 5.0 * voxel_size, 100)
     t_n = normals_enqueue(lib, cl, lists, 2.0 * voxel_size, 30, viewpoint)
-    return fpfh_enqueue(lib, cl, t_n, lists, False)
+    return fpfh_enqueue(lib, cl, t_n, lists, False), t_n
 
 
 class Matches(collections.namedtuple("Matches", "buf nn10 rows counts")):

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Relative transform between two lidar keyframes on an MI355X: FPFH features, mutual matches, the robust coarse fit
-and batched point-to-point ICP.
+and batched ICP (point-to-point by default, point-to-plane with `estimation="point_to_plane"`).
 
 Counterpart of cslam/lidar_pr/icp_utils.py (`compute_transform`, called by lidar_handler_node.py:115,133 for every
 accepted ScanContext match).  The reference runs FPFH + mutual nearest neighbours + TEASER++ for a coarse alignment and
@@ -36,8 +36,9 @@ from ._batch import gpu, rows, upload
 from .fpfh import (FM_BLOCK, FM_CHUNK, FM_MAX_DIM, FM_MAX_LANES, FPFH_BINS, KNN_BLOCK, KNN_CAND, KNN_CHUNK, KNN_MAX_NN,  # noqa: F401
                    compute_fpfh_feature, estimate_normals, estimate_normals_clouds, extract_fpfh, extract_fpfh_clouds,
                    find_correspondences, find_correspondences_pairs, find_knn, radius_neighbors, radius_neighbors_clouds)
-from .icp import (DEFAULT_STAGES, ICP_CHUNK, ICP_MAX_LANES, RegistrationResult, Rt2T, nearest_correspondences,  # noqa: F401
-                  register_pairs, registration_icp, registration_icp_pairs, yaw_seed)
+from .icp import (DEFAULT_STAGES, ESTIMATIONS, ICP_CHUNK, ICP_MAX_LANES, NORMALS_MAX_NN, NORMALS_RADIUS,  # noqa: F401
+                  RegistrationResult, Rt2T, nearest_correspondences, register_pairs, registration_icp, registration_icp_pairs,
+                  yaw_seed)
 from .robust import (ROBUST_DEFAULT_NODE_BUDGET, ROBUST_GRAPH_BLOCK, ROBUST_GRAPH_CHUNK, ROBUST_MAX_N, ROBUST_STACK_DEPTH,  # noqa: F401
                      RobustFit, consistency_graph, consistency_graph_pairs, max_clique, max_clique_graphs, robust_fit_pairs,
                      robust_rotation, robust_rotation_pairs, robust_translation, robust_translation_pairs)
@@ -85,13 +86,15 @@ class TeaserSuccess(Success):
             self.ok, self.clique_size, self.matches, self.certified, self.fitness, self.inlier_rmse)
 
 
-def solve_teaser_pairs(pairs, voxel_size, min_inliers, node_budget=ROBUST_DEFAULT_NODE_BUDGET, device=0):
+def solve_teaser_pairs(pairs, voxel_size, min_inliers, node_budget=ROBUST_DEFAULT_NODE_BUDGET, device=0,
+                       estimation="point_to_point"):
     """The reference's `solve_teaser` (icp_utils.py:103-139) for a list of (src, dst) pairs in ONE batched chain on the
     device: one upload, FPFH of all 2n clouds, mutual matches, the robust fit with noise_bound = voxel_size, and
     `registration_icp(voxel_size, 100 iterations)` from the fit's transforms.  Returns per pair (valid, translation,
     rotation) with dst ~ rotation . src + translation; `valid` is a `TeaserSuccess`: clique size > min_inliers.  A pair
-    that is not valid returns the unrefined fit, as the reference does."""
-    c, budget = robust.noise(voxel_size), robust.budget_of(node_budget)
+    that is not valid returns the unrefined fit, as the reference does.  estimation="point_to_plane": the refinement uses
+    the targets' normals that the FPFH step has computed anyway."""
+    c, budget, use_plane = robust.noise(voxel_size), robust.budget_of(node_budget), icp.plane(estimation)
     pairs = list(pairs)
     srcs = [rows(s, finite=True) for s, _ in pairs]
     dsts = [rows(d, finite=True) for _, d in pairs]
@@ -102,11 +105,12 @@ def solve_teaser_pairs(pairs, voxel_size, min_inliers, node_budget=ROBUST_DEFAUL
         if not pairs:
             return []
         both, a, b = upload(srcs + dsts, dev, pairs=True)                # the sources, then the targets
-        t_f = fpfh.extract_enqueue(lib, both, c, (0.0, 0.0, 0.0))
+        t_f, t_n = fpfh.extract_with_normals_enqueue(lib, both, c, (0.0, 0.0, 0.0))
         m = fpfh.match_enqueue(lib, a._replace(buf=t_f, rows=t_f.data_ptr()),
                                b._replace(buf=t_f, rows=t_f[int(a.off[-1]):].data_ptr()), FPFH_BINS)
         t_T, t_info, t_clique = robust.fit_enqueue(lib, a, b, m.ptr(m.rows), a.d_off, m.ptr(m.counts), c, budget, a.off, None)
-        t_ref, t_stats = icp.register_enqueue(lib, a, b, t_T.data_ptr(), np.array([c]), np.array([100], dtype=np.int32), 1e-6, 1e-6)
+        t_ref, t_stats = icp.register_enqueue(lib, a, b, t_T.data_ptr(), np.array([c]), np.array([100], dtype=np.int32), 1e-6, 1e-6,
+                                              t_n[int(a.off[-1]):].data_ptr() if use_plane else None)
         out = torch.cat((t_T, t_ref, t_stats, t_info.to(torch.float64)), dim=1).cpu().numpy()     # one copy of the results
         clique = t_clique.cpu().numpy()
     fits = robust.fits(out[:, :16], out[:, 36:42].astype(np.int64), clique, a.off)
@@ -119,10 +123,10 @@ def solve_teaser_pairs(pairs, voxel_size, min_inliers, node_budget=ROBUST_DEFAUL
     return results
 
 
-def solve_teaser(src, dst, voxel_size, min_inliers, node_budget=ROBUST_DEFAULT_NODE_BUDGET, device=0):
+def solve_teaser(src, dst, voxel_size, min_inliers, node_budget=ROBUST_DEFAULT_NODE_BUDGET, device=0, estimation="point_to_point"):
     """Counterpart of the reference's solve_teaser (icp_utils.py:103-139), same name and argument order: (valid,
     translation, rotation)."""
-    return solve_teaser_pairs([(src, dst)], voxel_size, min_inliers, node_budget, device)[0]
+    return solve_teaser_pairs([(src, dst)], voxel_size, min_inliers, node_budget, device, estimation)[0]
 
 
 def _accept(result, min_inliers, min_fitness):
@@ -135,17 +139,19 @@ def _coarse(coarse):
     return coarse
 
 
-def solve_icp(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0, coarse="yaw"):
+def solve_icp(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0, coarse="yaw", estimation="point_to_point"):
     """Counterpart of the reference's solve_teaser (icp_utils.py:103-139): (valid, translation, rotation) with
     dst ~ rotation . src + translation.  coarse="teaser": `solve_teaser` itself (`init_yaw_deg` and `min_fitness` are
-    not used)."""
+    not used).  `estimation`: as for `compute_transform`."""
+    icp.plane(estimation)
     if _coarse(coarse) == "teaser":
-        return solve_teaser(src, dst, voxel_size, min_inliers)
-    r = register_pairs([(src, dst)], voxel_size, init_yaw_deg)[0]
+        return solve_teaser(src, dst, voxel_size, min_inliers, estimation=estimation)
+    r = register_pairs([(src, dst)], voxel_size, init_yaw_deg, estimation=estimation)[0]
     return _accept(r, min_inliers, min_fitness), r.transformation[:3, 3].copy(), r.transformation[:3, :3].copy()
 
 
-def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0, coarse="yaw"):
+def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_fitness=0.0, coarse="yaw",
+                      estimation="point_to_point"):
     """Computes a 3D transform between 2 point clouds (reference icp_utils.py:178-196), dst ~ R . src + t, as
     registration_icp(source=src, target=dst) gives it.
 
@@ -158,6 +164,13 @@ def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_
         coarse: "yaw" (the default: the staged ICP from the ScanContext yaw, as described above) or "teaser": the
             reference's own path, `solve_teaser` -- FPFH, mutual matches, the robust fit, one ICP stage; `init_yaw_deg`
             and `min_fitness` are not used, and the success flag is the reference's: clique size > min_inliers
+        estimation: "point_to_point" (the default: the reference's estimator) or "point_to_plane": open3d's
+            TransformationEstimationPointToPlane on the targets' normals, which are estimated on the device from the
+            neighbours within 2 voxels (30 at most), as the reference's `extract_fpfh` does.  On street scenes (ground and
+            walls, which slide under point-to-point) it needs about a third of the updates.  Its basin is narrower: a single
+            stage at the voxel radius from a yaw seed 3 degrees off can diverge where point-to-point converges, so with
+            coarse="yaw" it relies on the coarse stages, and it is not the default.  A singular system (fewer than six
+            correspondences, all normals parallel, |det| < 1e-6) leaves the transform as it is.
 
     Returns:
         (Transform, Success): the transform message and a success flag that is truthy / falsy like the reference's bool
@@ -169,10 +182,11 @@ def compute_transform(src, dst, voxel_size, min_inliers, init_yaw_deg=None, min_
     fitness of about 0.6 (thousands of "inliers"), a right one is above 0.9 on the same clouds.  Set `min_fitness`, or
     use coarse="teaser", whose test is the clique itself.
     """
+    icp.plane(estimation)
     if _coarse(coarse) == "teaser":
-        valid, t, R = solve_teaser(src, dst, voxel_size, min_inliers)
+        valid, t, R = solve_teaser(src, dst, voxel_size, min_inliers, estimation=estimation)
         return to_transform_msg(t, R), valid
-    r = register_pairs([(src, dst)], voxel_size, init_yaw_deg)[0]
+    r = register_pairs([(src, dst)], voxel_size, init_yaw_deg, estimation=estimation)[0]
     transform = to_transform_msg(r.transformation[:3, 3], r.transformation[:3, :3])
     return transform, Success(_accept(r, min_inliers, min_fitness), r)
 

@@ -398,6 +398,32 @@ int cslam_icp_register_dev(const double *d_src, const int64_t *d_src_off, const 
                            const int64_t *d_dst_off, int n_pairs, const double *d_init, const double *max_dist,
                            const int *max_iter, int n_stages, double rel_fitness, double rel_rmse, double *d_T_out,
                            double *d_stats_out, void *stream);
+/* register_plane: the same loop with open3d's TransformationEstimationPointToPlane as the update.  Correspondences, fitness,
+ *   inlier_rmse, the stopping rule, the stages and every argument and check are those of cslam_icp_register_dev (open3d
+ *   evaluates a registration the same way whatever the estimator); d_dst_normals [total target rows, 3] holds the targets'
+ *   normals in the layout of d_dst (NULL: CSLAM_E_INVALID, "d_dst_normals is NULL").  cslam_normals_dev computes them.
+ *   The update, float64 throughout (csrc/plane.h), for the kept correspondences (p = T . src_i, q its target point, n the
+ *   normal at q):
+ *     r = (p - q) . n,   J = [(p - o) x n, n],   A = sum J J^T,   b = sum J r   (29 sums per block: n, sum d^2, the 21
+ *     upper-triangle entries of A, the 6 of b; the same fixed shuffle tree and block order as the 17 of the rigid fit,
+ *     no float atomics: a pair's result is the same bits alone or in any batch),
+ *   o the pair's sum origin as above (zero for clouds around the frame origin: the sums are then open3d's as written).
+ *   The shift is needed: p x n of frame coordinates far from the origin couples the rotation and translation columns of
+ *   A (condition 2.8e3 at the origin, 7.8e18 for the same clouds at (2^17, -2^16, 1024) m); det A is the same in both frames.
+ *   Solve: x = -A^-1 b by an unpivoted LDL^T of the symmetric 6 x 6, det A = the product of D.  The update is the
+ *     IDENTITY when fewer than six correspondences are kept (rank A < 6: det A = 0 exactly), a pivot is exactly 0, det A is
+ *     NaN, infinite or |det A| < 1e-6, or the solution is not finite.  This restates the determinant check of open3d's
+ *     SolveLinearSystemPSD from memory; no open3d is available to pin it against, so parity with open3d is NOT pinned.
+ *   Compose: U' = (Rz(x2) . Ry(x1) . Rx(x0), (x3, x4, x5)) (open3d's TransformVector6dToMatrix4d), the translation moved
+ *     back to the frame, t = t' + o - R o, and T <- U . T as above.
+ *   Known weakness: the 1e-6 threshold is absolute.  A scene with ONE sliding direction (two plane families that share a
+ *     line) has a computed determinant far above it and takes whatever step the solve gives; that is open3d's behaviour and
+ *     it is kept.  Point-to-plane also has the narrower basin of convergence: from a ScanContext yaw seed (up to 3 degrees
+ *     off) run it through coarse stages (4x, 2x, 1x the voxel size), not in one stage at the voxel radius. */
+int cslam_icp_register_plane_dev(const double *d_src, const int64_t *d_src_off, const double *d_dst,
+                                 const int64_t *d_dst_off, const double *d_dst_normals, int n_pairs,
+                                 const double *d_init, const double *max_dist, const int *max_iter, int n_stages,
+                                 double rel_fitness, double rel_rmse, double *d_T_out, double *d_stats_out, void *stream);
 
 /* Lidar keyframes: batched voxel down-sampling, the step every keyframe goes through before it is stored
  * (cslam/lidar_pr/icp_utils.py:93-100 `downsample`: drop the rows with a non-finite coordinate, then open3d's

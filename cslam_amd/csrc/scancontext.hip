@@ -16,13 +16,24 @@
 //                  roll-and-recompute loop, same sums in the same order.
 //   sc_pick      : first strict minimum over the candidates in ring-key order, from 1.0
 //                  (scancontext_matching.py:64-75).
-// All arithmetic is float64 in the order of oracle/sc_oracle.c (left-to-right fma chains).
+// All arithmetic is float64 in the order of oracle/sc_oracle.c (left-to-right fma chains).  This file is compiled with
+// -ffp-contract=off (Makefile): the only fused multiply-adds are the fma() calls written here.  __dmul_rn and
+// __dadd_rn alone do not stop the compiler from fusing, and a fused 180 - k * atan(..) moved points that lie on a
+// sector edge into the neighbouring sector.
 #include <new>
 #include "common.h"
+#include "atan_cr.h"
 
 #define SC_MAX_CAND 64
 #define SC_MAX_R 64
 #define SC_MAX_S 128
+#define SC_MAX_LDS (160 * 1024)     // one workgroup's LDS on gfx950
+
+// LDS of sc_distance_kernel: both scan contexts [R][S], two column-norm rows and the per-shift similarities [S],
+// the cosine matrix [S][S+1], all float64.  A bank is only created for a shape whose search fits.
+static size_t sc_distance_lds_bytes(int R, int S) {
+    return ((size_t)2 * R * S + (size_t)3 * S + (size_t)S * (S + 1)) * 8;
+}
 
 struct cslam_scbank {
     int device, R, S, L;
@@ -84,6 +95,9 @@ CSLAM_API int cslam_scbank_create(int device, int rings, int sectors, int64_t ca
     ARG_CHECK(out, "out is NULL");
     ARG_CHECK(rings >= 1 && rings <= SC_MAX_R, "rings must be in [1, 64]");
     ARG_CHECK(sectors >= 1 && sectors <= SC_MAX_S, "sectors must be in [1, 128]");
+    ARG_CHECK(sc_distance_lds_bytes(rings, sectors) <= SC_MAX_LDS,
+              "rings x sectors cannot be searched: 8 * (2*rings*sectors + 3*sectors + sectors*(sectors+1)) bytes of LDS "
+              "must not exceed 163840 (64 x 91 and 14 x 128 fit, 20 x 128 does not)");
     DeviceGuard _dev_guard(device);
     if (!_dev_guard.ok) { cslam_set_error("hipSetDevice(%d) failed", device); return CSLAM_E_HIP; }
     cslam_scbank *b = new (std::nothrow) cslam_scbank();
@@ -515,7 +529,7 @@ CSLAM_API int cslam_scbank_search_dev(cslam_scbank_t *b, const double *d_q, int6
     HIP_TRY(hipGetLastError());
     hipLaunchKernelGGL(sc_knn_merge_kernel, dim3((unsigned)nq), dim3(64), 0, st, pk, pi, G, C, cand);
     HIP_TRY(hipGetLastError());
-    const size_t lds = ((size_t)2 * R * S + 3 * S + (size_t)S * (S + 1)) * 8;
+    const size_t lds = sc_distance_lds_bytes(R, S);      // <= SC_MAX_LDS, checked at create
     HIP_TRY(hipFuncSetAttribute((const void *)sc_distance_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
                                 (int)lds));
     hipLaunchKernelGGL(sc_distance_kernel, dim3((unsigned)C, (unsigned)nq), dim3(256), lds, st, b->sc, b->cn, d_q,
@@ -570,6 +584,10 @@ CSLAM_API int cslam_scbank_search_host(cslam_scbank_t *b, const double *queries,
 // cap is honoured without serialising the points: per 1024-point chunk every wave ranks its lanes within
 // equal-bin groups (ballot), per-wave bin totals are prefix-summed across the 16 waves per bin, and a
 // point takes part iff (points of its bin before it) < 500.
+// The arctangent is atan_cr (atan_cr.h), correctly rounded: a point on a sector edge (an angle that is a multiple of
+// the sector width) changes bin with its last bit.  The oracle and the reference call libm's atan, which is off in
+// the last bit for about one argument in a thousand: "bit for bit" holds for the descriptor unless such an argument
+// also lies on a sector edge.
 #define SCD_WAVES 16
 #define SCD_CAP 500
 #define SCD_MAX_BINS 2048
@@ -596,7 +614,7 @@ __device__ __forceinline__ double f64_unordered(unsigned long long u) {
 
 __global__ __launch_bounds__(SCD_WAVES * 64) void sc_from_cloud_kernel(
     const double *__restrict__ pts, const int64_t *__restrict__ offsets, int R, int S, double gap_ring,
-    double gap_sector, double *__restrict__ out, int *__restrict__ bad_sector) {
+    double gap_sector, double *__restrict__ out, int *__restrict__ status) {
     __shared__ int s_cnt[SCD_MAX_BINS];
     __shared__ unsigned long long s_max[SCD_MAX_BINS];
     __shared__ unsigned short s_hist[SCD_WAVES][SCD_MAX_BINS];
@@ -618,17 +636,21 @@ __global__ __launch_bounds__(SCD_WAVES * 64) void sc_from_cloud_kernel(
                 if (x == 0.0) x = 0.001;
                 if (y == 0.0) y = 0.001;
                 double theta;
-                if (x >= 0 && y >= 0) theta = __dmul_rn(k, atan(__ddiv_rn(y, x)));
-                else if (x < 0 && y >= 0) theta = __dsub_rn(180.0, __dmul_rn(k, atan(__ddiv_rn(y, -x))));
-                else if (x < 0 && y < 0) theta = __dadd_rn(180.0, __dmul_rn(k, atan(__ddiv_rn(y, x))));
-                else theta = __dsub_rn(360.0, __dmul_rn(k, atan(__ddiv_rn(-y, x))));
+                if (x >= 0 && y >= 0) theta = __dmul_rn(k, atan_cr(__ddiv_rn(y, x)));
+                else if (x < 0 && y >= 0) theta = __dsub_rn(180.0, __dmul_rn(k, atan_cr(__ddiv_rn(y, -x))));
+                else if (x < 0 && y < 0) theta = __dadd_rn(180.0, __dmul_rn(k, atan_cr(__ddiv_rn(y, x))));
+                else theta = __dsub_rn(360.0, __dmul_rn(k, atan_cr(__ddiv_rn(-y, x))));
                 const double far = sqrt(__dadd_rn(__dmul_rn(x, x), __dmul_rn(y, y)));
                 double ring = np_floordiv_pos(far, gap_ring);
                 const double sector = np_floordiv_pos(theta, gap_sector);
                 if (ring >= (double)R) ring = (double)(R - 1);
-                const int is = (int)sector;
-                if (is < 0 || is >= S) atomicOr(bad_sector, 1);      // the reference raises IndexError
-                else bin = (int)ring * S + is;
+                if (ring != ring || sector != sector) {
+                    atomicOr(status, 2);                                 // int(nan): the reference raises ValueError
+                } else {                                                 // the casts only after the NaN test
+                    const int is = (int)sector;
+                    if (is < 0 || is >= S) atomicOr(status, 1);          // the reference raises IndexError
+                    else bin = (int)ring * S + is;
+                }
             }
         }
         // rank among the equal-bin lanes of this wave, and the wave's total per bin

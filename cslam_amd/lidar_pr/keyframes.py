@@ -19,7 +19,7 @@ def ingest(clouds, voxel_size, device=0):
     """(descriptors, downsampled) of a list of raw clouds ([n, >=3] arrays or objects with `.points`).
 
     descriptors: [len(clouds), RINGS * SECTORS] float64, the rows `ScanContext.compute_embeddings` gives for the same
-    clouds; a point at exactly 360 degrees raises the same IndexError.
+    clouds; a point at exactly 360 degrees raises the same IndexError, an infinite x or y the same ValueError.
     downsampled: the list `icp_utils.downsample_clouds(clouds, voxel_size)` gives (`VoxelSizeError` likewise)."""
     with gpu(device) as (lib, dev):
         clouds = [rows(c) for c in clouds]
@@ -33,7 +33,8 @@ def ingest(clouds, voxel_size, device=0):
         scancontext.enqueue(lib, cl.rows, cl.d_off, n, RINGS, SECTORS, MAX_LENGTH, base, base + desc_bytes)
         host = t_out.cpu().numpy()
     at = lay["extra"]
-    if int(host[at + desc_bytes:at + desc_bytes + 4].view(np.int32)[0]) != 0:
-        raise scancontext.theta_360_error(SECTORS)
+    err = scancontext.status_error(int(host[at + desc_bytes:at + desc_bytes + 4].view(np.int32)[0]), SECTORS)
+    if err is not None:
+        raise err
     desc = host[at:at + desc_bytes].view(np.float64).reshape(n, RINGS * SECTORS).copy()
     return desc, voxel.unpack(host, lay, n, False)

@@ -23,6 +23,22 @@ def theta_360_error(sectors):
                       "as in the reference's ptcloud2sc)" % (sectors, sectors))
 
 
+def nan_index_error():
+    """The reference's failure for a point whose ring or sector index is NaN (infinite x or y, or x*x overflowing):
+    pt2rs ends in int(nan)."""
+    return ValueError("cannot convert float NaN to integer")
+
+
+def status_error(status, sectors):
+    """The exception for `*d_status` of `cslam_scancontext_from_cloud_dev`, or None.  With both bits set ValueError wins:
+    a batch has no first failing point to follow."""
+    if status & 2:
+        return nan_index_error()
+    if status & 1:
+        return theta_360_error(sectors)
+    return None
+
+
 def enqueue(lib, p_points, p_offsets, n, rings, sectors, max_length, p_out, p_status):
     """`cslam_scancontext_from_cloud_dev` on device pointers, on the current stream (`keyframes.ingest` shares it)."""
     import torch
@@ -63,6 +79,7 @@ class ScanContext:
             enqueue(self._lib, pts.data_ptr(), off.data_ptr(), len(clouds), self.shape[0], self.shape[1], self.max_length,
                     out.data_ptr(), status.data_ptr())
         res = out.cpu().numpy()
-        if int(status.item()) != 0:
-            raise theta_360_error(self.shape[1])
+        err = status_error(int(status.item()), self.shape[1])
+        if err is not None:
+            raise err
         return res

@@ -335,6 +335,10 @@ int cslam_mac_fw_subset(int64_t num_poses, int64_t n_fixed, const int64_t *fixed
  *              row_limit[j] (optional) hides bank rows >= row_limit[j] from query j.
  *              cand / cdist / cyaw [nq, num_candidates] are optional (NULL) diagnostics: candidate
  *              rows (-1 = bank smaller than num_candidates), their distances and yaw shifts.
+ *   create   : rings in [1, 64], sectors in [1, 128], and stage 2 must fit one workgroup's LDS:
+ *              8 * (2*rings*sectors + 3*sectors + sectors*(sectors+1)) <= 163840 bytes (64 x 91 and 14 x 128 are
+ *              the largest such shapes; 20 x 128 is not one).  Any other shape is CSLAM_E_INVALID at create, so
+ *              that no bank exists that no search can serve.
  */
 typedef struct cslam_scbank cslam_scbank_t;
 int cslam_scbank_create(int device, int rings, int sectors, int64_t capacity_hint, cslam_scbank_t **out);
@@ -358,8 +362,12 @@ int cslam_scbank_search_dev(cslam_scbank_t *bank, const double *d_queries, int64
  * d_points: all frames concatenated, [total_points, 3]; frame f owns rows d_offsets[f] .. d_offsets[f+1]-1.
  * d_out [n_frames, rings*sectors] float64.  NaN points are skipped; a bin keeps the maximum of z + 2 over
  * its first 500 points in cloud order (the reference's storage cap), 0.0 when its storage has unused slots.
- * *d_status (device int32) is set non-zero when a point has theta == 360 exactly, where the reference
- * raises IndexError (the point is skipped here). */
+ * *d_status (device int32) is a bit set over all frames of the call; a point that sets a bit is skipped:
+ *   bit 0: a point has theta == 360 exactly, where the reference raises IndexError;
+ *   bit 1: a point's ring or sector index is NaN (x or y infinite, or so large that x*x + y*y overflows), where
+ *          the reference raises ValueError ("cannot convert float NaN to integer").
+ * The reference raises at the first such point of one cloud; a batch has no such order, so a caller that finds
+ * both bits set raises ValueError.  An infinite z alone sets nothing: the bin holds +-inf, as in the reference. */
 int cslam_scancontext_from_cloud_dev(const double *d_points, const int64_t *d_offsets, int n_frames,
                                      int rings, int sectors, double max_length, double *d_out,
                                      int32_t *d_status, void *stream);

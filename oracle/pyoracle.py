@@ -108,6 +108,8 @@ def ptcloud2sc(points, shape=(20, 60), max_length=80.0):
     sc = np.empty(shape, dtype=np.float64)
     lib.oracle_ptcloud2sc.argtypes = [C.c_void_p, C.c_int64, C.c_int, C.c_int, C.c_double, C.c_void_p]
     rc = lib.oracle_ptcloud2sc(_p(pts), pts.shape[0], shape[0], shape[1], float(max_length), _p(sc))
+    if rc == -3:
+        raise ValueError("cannot convert float NaN to integer")      # the reference's int(idx_ring) / int(idx_sector)
     if rc == -2:
         raise IndexError("sector index out of range (theta == 360), as in the reference")
     assert rc == 0

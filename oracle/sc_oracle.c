@@ -137,7 +137,11 @@ API int oracle_sc_search(const double *bank, int64_t n, int R, int S, const doub
 /* ---- descriptor: oracle_ptcloud2sc <- cslam/lidar_pr/scancontext_utils.py:10-75 (xy2theta, pt2rs,
  * ptcloud2sc) for float64 clouds [n,3].  Every bin keeps the maximum of point[2] + 2.0 over the first
  * 500 points that fall in it (in cloud order; the reference's `enough_large` storage) and 0.0 for the
- * unused storage slots.  np.divmod is restated from numpy's npy_divmod. */
+ * unused storage slots.  np.divmod is restated from numpy's npy_divmod.  atan is libm's, as numpy's is: its last bit
+ * is not correctly rounded everywhere, the kernel's (csrc/atan_cr.h) is, so the two can differ for a point that lies
+ * on a sector edge within that bit.  Returns 0, or the code of the first
+ * point at which the reference raises: -3 for a ring or sector index that is NaN (an infinite x or y, or an
+ * x*x that overflows; ValueError from int(nan)), -2 for theta == 360 (IndexError). */
 static double np_floordiv(double a, double b) {
     double mod = fmod(a, b);
     double div = (a - mod) / b;
@@ -170,6 +174,7 @@ API int oracle_ptcloud2sc(const double *pts, int64_t n, int R, int S, double max
         double far = sqrt(x * x + y * y);
         double ring = np_floordiv(far, gap_ring), sector = np_floordiv(theta, gap_sector);
         if (ring >= R) ring = R - 1;
+        if (isnan(ring) || isnan(sector)) { free(cnt); return -3; }   /* int(nan): the reference raises ValueError */
         int ir = (int)ring, is = (int)sector;
         if (is < 0 || is >= S) { free(cnt); return -2; }     /* the reference raises IndexError */
         int b = ir * S + is;

@@ -92,6 +92,16 @@ _SIGNATURES = {
     "cslam_fiedler_start_block": (_i, [C.c_uint32, _i64, _vp]),
     "cslam_fiedler_release": (_i, []),
     "cslam_mac_fw_subset": (_i, [_i64, _i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_pgo_plan": (_i, [_i64, _i64, _vp, _vp, _i64, _vp]),
+    "cslam_pgo_linearize_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_pgo_system_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_pgo_solve_dev": (_i, [C.c_double, _vp, _vp, _vp, _vp]),
+    "cslam_pgo_retract_dev": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "cslam_pgo_cost_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_pgo_weights_dev": (_i, [_vp, _i64, C.c_double, C.c_double, _vp, _vp, _vp]),
+    "cslam_pgo_optimize": (_i, [_i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_pgo_trace": (_i, [_vp, _i64, _vp]),
+    "cslam_pgo_release": (_i, []),
     "cslam_scbank_create": (_i, [_i, _i, _i, _i64, _vp]),
     "cslam_scbank_destroy": (_i, [_vp]),
     "cslam_scbank_size": (_i, [_vp, _vp, _vp, _vp]),

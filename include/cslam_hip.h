@@ -319,6 +319,60 @@ int cslam_mac_fw_subset(int64_t num_poses, int64_t n_fixed, const int64_t *fixed
                         void *stream);
 
 /* ------------------------------------------------------------------------------------------------
+ * Pose-graph back end: GNC-TLS around Levenberg-Marquardt on SE(3).
+ * Replaces src/back_end/decentralized_pgo.cpp:797-827 (DecentralizedPGO::optimize: GncOptimizer<GncParams<
+ * LevenbergMarquardtParams>> over the aggregated graph), :64-70 (default sigmas 0.01 rad / 0.1 m), :843-845 (the prior on
+ * the first pose) and the BetweenFactor<Pose3> edges of src/back_end/gtsam_utils.cpp:58-89.  GTSAM is third party and was
+ * not available to compare against: the algorithm is the one csrc/pgo.hip states, tests/pgo_reference.py its float64 yardstick.
+ *
+ * Conventions: poses and measurements are 4 x 4 row-major float64 (16 doubles); the tangent is GTSAM's [omega, v]; factor k
+ * in [0, nf) is the between factor (ei[k], ej[k]) with residual Log(Z_k^-1 T_i^-1 T_j), factor nf is the prior on pose `prior`
+ * with residual Log(Z_nf^-1 T_prior); sigmas are [nf + 1][6]; E_k = 1/2 sum (e / sigma)^2; the cost is sum w_k E_k.
+ * The entries share ONE workspace (grow-only, on the current device, freed by cslam_pgo_release) and are serialised by a lock.
+ * No floating-point atomics anywhere: the same input gives the same bits. */
+/* Structure pass (csrc/pgo_plan.h) of the edge list and upload of its index lists; every staged entry below works on the
+ * graph of the last call.  CSLAM_E_INVALID on i == j or an index out of range, CSLAM_E_LIMIT on more junctions than the dense
+ * junction system holds; both before anything touches HIP.  h_info (optional) [8]: junctions, segments, interior poses,
+ * distinct pose pairs, poses promoted by the PGO_SEG_MAX cut, longest segment, PGO_SEG_MAX, the junction cap. */
+int cslam_pgo_plan(int64_t n, int64_t nf, const int32_t *h_ei, const int32_t *h_ej, int64_t prior, int64_t *h_info);
+/* decentralized_pgo.cpp:797-827 (what NonlinearFactorGraph::linearize does inside the LM iteration): E_k [nf + 1] to d_E and
+ * the whitened (sqrt(w_k) / sigma) normal equations -- 6 x 6 diagonal block and gradient per pose, one block per pose pair --
+ * to the workspace; cslam_pgo_system_host copies them out: h_Hdiag [n][36], h_g [n][6], h_Hoff [pairs][36] = block (row
+ * h_pa, column h_pb), h_pa < h_pb sorted; any pointer may be NULL. */
+int cslam_pgo_linearize_dev(const double *d_poses, const double *d_meas, const double *d_sigmas, const double *d_weights,
+                            double *d_E, void *stream);
+int cslam_pgo_system_host(double *h_Hdiag, double *h_g, double *h_Hoff, int32_t *h_pa, int32_t *h_pb, void *stream);
+/* (H + lambda I) delta = -g on the system of the last linearise (LevenbergMarquardtOptimizer's damped solve, lambda I as
+ * the reference's default, not the diagonal): segments by block recurrence, junctions by dense Cholesky, back substitution.
+ * d_delta [n][6]; *h_status 0, or 1 on a non-positive pivot (nothing aborts; delta is then meaningless);
+ * *h_predicted = -(g . delta + 1/2 delta . H delta), the decrease the quadratic model predicts. */
+int cslam_pgo_solve_dev(double lambda, double *d_delta, int *h_status, double *h_predicted, void *stream);
+/* Pose3::retract with the full exponential: out_v = T_v Exp(delta_v).  Needs no plan. */
+int cslam_pgo_retract_dev(const double *d_poses, const double *d_delta, int64_t n, double *d_out, void *stream);
+/* NonlinearFactorGraph::error of the weighted graph: E_k to d_E, *h_cost = sum w_k E_k (block partials in block order). */
+int cslam_pgo_cost_dev(const double *d_poses, const double *d_meas, const double *d_sigmas, const double *d_weights, double *d_E,
+                       double *h_cost, void *stream);
+/* GncOptimizer::calculateWeights, TLS: 0 at E >= (mu + 1) / mu barc2, 1 at E <= mu / (mu + 1) barc2,
+ * sqrt(barc2 mu (mu + 1) / E) - mu between; d_known (optional, bytes): known inliers keep 1.  Needs no plan. */
+int cslam_pgo_weights_dev(const double *d_E, int64_t nfac, double mu, double barc2, const uint8_t *d_known, double *d_w,
+                          void *stream);
+/* The whole of DecentralizedPGO::optimize (decentralized_pgo.cpp:797-827) on HOST arrays, for a host without Python.
+ *   h_poses [n][16]      initial estimate in, result out
+ *   h_meas [nf + 1][16], h_sigmas [nf + 1][6] (positive, finite: CSLAM_E_INVALID otherwise), h_known [nf + 1] bytes or NULL
+ *   h_params             NULL = the reference's defaults, or [12]: lambda_0 1e-5, lambda factor 10, lambda upper bound 1e5,
+ *                        LM iterations 100, relative 1e-5 and absolute 1e-5 error tolerance, model fidelity 1e-3, GNC rounds
+ *                        100, mu step 1.4, GNC relative cost tolerance 1e-5, weights tolerance 1e-4, barc^2 (1/2 chi2inv(0.99, 6))
+ *   h_weights [nf + 1]   final GNC weights
+ *   h_info [8]           GNC rounds, LM iterations, solves, final cost, final lambda, status (1: some trial step met a
+ *                        non-positive pivot and was rejected), junctions, segments
+ * cslam_pgo_trace: accept (1) / reject (0) of every trial step of the last call, in order. */
+int cslam_pgo_optimize(int64_t n, int64_t nf, const int32_t *h_ei, const int32_t *h_ej, int64_t prior, double *h_poses,
+                       const double *h_meas, const double *h_sigmas, const uint8_t *h_known, const double *h_params,
+                       double *h_weights, double *h_info);
+int cslam_pgo_trace(int32_t *h_out, int64_t cap, int64_t *h_count);
+int cslam_pgo_release(void);
+
+/* ------------------------------------------------------------------------------------------------
  * Lidar place recognition: ScanContext bank.
  * Replaces cslam/lidar_pr/scancontext_matching.py:5-104 (ScanContextMatching) with its helpers
  * scancontext_utils.py:78-79 (sc2rk) and :81-113 (distance_sc).  Scan contexts are float64

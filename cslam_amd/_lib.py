@@ -137,6 +137,11 @@ _SIGNATURES = {
     "cslam_robust_rotation_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
     "cslam_robust_translation_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp]),
     "cslam_robust_fit_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_vis_match_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_vis_pnp_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _i, _i, C.c_uint64, _vp, _vp, _vp, _vp]),
+    "cslam_vis_register_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, C.c_double, _i, _i, _i, C.c_uint64,
+                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_vis_hypotheses_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_wino4_fused_c64_h_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_h_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_r_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),
@@ -178,7 +183,7 @@ _SIGNATURES = {
 EXPERIMENTAL_SYMBOLS = ("cslam_wino4_input_h3_dev", "cslam_wino2_fused64_dev", "cslam_wino2_fused_c64_dev",
                         "cslam_wino4_fused_c64_dev", "cslam_debug_wfh_prof_dev", "cslam_peak_copy_dev", "cslam_peak_mfma_dev",
                         "cslam_debug_last_candidates", "cslam_ring_schedule_describe", "cslam_trunk_timing", "cslam_trunk_timing_read",
-                        "cslam_voxel_profile", "cslam_voxel_profile_read")
+                        "cslam_voxel_profile", "cslam_voxel_profile_read", "cslam_vis_hypotheses_dev")
 EXPORTED_SYMBOLS = tuple(n for n in _SIGNATURES if n not in EXPERIMENTAL_SYMBOLS)
 
 

@@ -1,0 +1,258 @@
+"""Geometric verification of a visual loop closure on the GPU (csrc/vis.hip, csrc/pnp.h): nearest-neighbour matching of
+32-byte binary descriptors with a ratio test, then 3D -> 2D PnP inside RANSAC with refinement on the inliers.
+
+Replaces the `registration_.computeTransformation(from, to, ...)` calls of the reference's src/front_end/rgbd_handler.cpp:433-469
+(`receive_local_keyframe_match`, intra-robot) and :493-554 (`receive_local_image_descriptors`, inter-robot), whose keyframes
+carry 2D keypoints, their 3D points and their descriptors (:471-491); `frontend.pnp_min_inliers` = 20
+(map_manager_node.cpp:18).  Behind that call is rtabmap's visual registration, taken at its defaults (ratio 0.8, 300
+iterations, 2 px).  rtabmap and OpenCV are third party and were not available to compare against, so parity with them is
+unpinned: the algorithm is the one include/cslam_hip.h states and tests/vis_reference.py restates in float64.
+
+Convention: `transformation` maps points of the "from" camera frame into the "to" camera frame.  The 3D points come from
+"from"; the pixels and the camera (fx, fy, cx, cy: pinhole, rectified, no distortion) from "to".
+
+There is no CPU path: without the library or a GPU the functions raise CslamHipError.
+"""
+from collections import namedtuple
+
+import numpy as np
+
+from .. import _lib
+from ..back_end.pose_graph import DEFAULT_NOISE_STD, PoseGraphEdge
+from ..lidar_pr._batch import gpu, host, offsets, stream, to_dev
+
+VIS_MATCH_BLOCK = 256          # "from" rows per workgroup of the matcher
+VIS_MATCH_CHUNK = 256          # "to" rows per LDS chunk of the matcher; the tests size around both
+VIS_MAX_CORR = 2048            # most usable correspondences of a pair the PnP kernel attempts; above it: status 3
+VIS_DESC_BYTES = 32
+
+Keyframe = namedtuple("Keyframe", "keypoints points descriptors")
+Keyframe.__doc__ = """What a keyframe carries on the wire: keypoints [n, 2] pixels, points [n, 3] in the camera frame (a row
+that is not finite: no depth), descriptors [n, 32] uint8.  float32 arrays are widened to float64 on upload."""
+
+
+class VisualRegistration:
+    """The verification of one pair: `transformation` (4 x 4, "from" camera frame -> "to" camera frame), `success`
+    (status 0), `status` (0 accepted; 1 rejected: too few inliers, the best fit found; 2 fewer usable correspondences than
+    max(4, min_inliers): not attempted, the identity; 3 more than VIS_MAX_CORR: not attempted, the identity), `matches`
+    [K, 2] (from row, to row), `inliers` [K] bool, `dropped_no_depth`, `best_hypothesis` (-1: not attempted)."""
+
+    def __init__(self, transformation, success, status, matches, inliers, dropped_no_depth, best_hypothesis):
+        self.transformation = transformation
+        self.success = success
+        self.status = status
+        self.matches = matches
+        self.inliers = inliers
+        self.dropped_no_depth = dropped_no_depth
+        self.best_hypothesis = best_hypothesis
+
+    def __repr__(self):
+        return "VisualRegistration(status=%d, inliers=%d of %d matches, dropped_no_depth=%d, best_hypothesis=%d)" % (
+            self.status, int(np.count_nonzero(self.inliers)), len(self.matches), self.dropped_no_depth, self.best_hypothesis)
+
+    def to_edge(self, key_from, key_to, noise_std=DEFAULT_NOISE_STD):
+        """The closure as a `PoseGraphEdge` for back_end.pose_graph.optimize.  The between factor measures
+        pose(key_from)^-1 pose(key_to), the pose of the "to" camera in the "from" camera frame: the inverse of
+        `transformation`.  Raises for a registration that did not succeed."""
+        if not self.success:
+            raise ValueError("a registration with status %d is no loop closure" % self.status)
+        return PoseGraphEdge(tuple(key_from), tuple(key_to), np.linalg.inv(self.transformation), np.asarray(noise_std, dtype=np.float64))
+
+
+# ---- argument checks: everything that can be wrong raises here, before any launch ------------------------------------
+def _descriptors(d):
+    d = np.asarray(d)
+    if d.ndim != 2 or d.shape[1] != VIS_DESC_BYTES:
+        raise ValueError("descriptors are [n, %d] uint8 (ORB / BRIEF-32), got shape %s" % (VIS_DESC_BYTES, d.shape))
+    if d.dtype != np.uint8:
+        raise ValueError("descriptors are uint8, got %s" % d.dtype)
+    return np.ascontiguousarray(d)
+
+
+def _rows(a, width, what):
+    a = np.asarray(a)
+    if a.ndim != 2 or a.shape[1] != width:
+        raise ValueError("%s are an [n, %d] array, got shape %s" % (what, width, a.shape))
+    return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _keyframe(kf):
+    kp, pts, desc = _rows(kf.keypoints, 2, "keypoints"), _rows(kf.points, 3, "points"), _descriptors(kf.descriptors)
+    if not (len(kp) == len(pts) == len(desc)):
+        raise ValueError("a keyframe has one point and one descriptor per keypoint: %d, %d, %d" % (len(kp), len(pts), len(desc)))
+    return kp, pts, desc
+
+
+def _cameras(cameras, n):
+    cam = np.asarray(cameras, dtype=np.float64)
+    if cam.shape == (4,):
+        cam = np.repeat(cam[None], n, axis=0)
+    if cam.shape != (n, 4):
+        raise ValueError("cameras are (fx, fy, cx, cy), one for all pairs or one per pair: got shape %s for %d pairs" % (cam.shape, n))
+    if not (np.all(np.isfinite(cam)) and np.all(cam[:, :2] > 0.0)):
+        raise ValueError("intrinsics must be finite and fx, fy positive")
+    return np.ascontiguousarray(cam)
+
+
+def _nndr(nndr):
+    r = float(nndr)
+    if not 0.0 <= r <= 1.0:
+        raise ValueError("nndr must be in [0, 1]")
+    return r
+
+
+def _ransac(iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed):
+    it, e, mi, ri, rr, sd = int(iterations), float(reproj_error), int(min_inliers), int(refine_iterations), int(refine_rounds), int(seed)
+    if it < 1:
+        raise ValueError("iterations must be at least 1")
+    if not (np.isfinite(e) and e > 0.0):
+        raise ValueError("reproj_error must be positive and finite")
+    if mi < 1:
+        raise ValueError("min_inliers must be at least 1")
+    if ri < 0 or rr < 0:
+        raise ValueError("refine_iterations and refine_rounds must not be negative")
+    if not 0 <= sd < 2 ** 64:
+        raise ValueError("seed must fit 64 unsigned bits")
+    return it, e, mi, ri, rr, sd
+
+
+def _cat(arrays, width, dtype):
+    return np.concatenate(arrays, axis=0) if arrays else np.zeros((0, width), dtype=dtype)
+
+
+# ---- the launches, each written once ------------------------------------------------------------------------------
+def _outputs(n, total, dev):
+    import torch
+    return (torch.zeros((n, 16), dtype=torch.float64, device=dev), torch.zeros((n, 8), dtype=torch.int32, device=dev),
+            torch.zeros(max(total, 1), dtype=torch.int32, device=dev))
+
+
+def _registrations(T, info, flags, rows, off):
+    out = []
+    for p in range(len(T)):
+        k = int(info[p, 1])
+        out.append(VisualRegistration(T[p].reshape(4, 4).copy(), int(info[p, 0]) == 0, int(info[p, 0]),
+                                      rows[off[p]:off[p] + k].astype(np.int64), flags[off[p]:off[p] + k].astype(bool),
+                                      int(info[p, 3]), int(info[p, 5])))
+    return out
+
+
+def match_descriptors_pairs(pairs, nndr=0.8, device=0):
+    """Matches of a list of (descriptors_from [n, 32] uint8, descriptors_to [m, 32] uint8) in ONE call
+    (`cslam_vis_match_dev`): per pair rows [K, 2] int64 (from row, to row), ascending in the from row.  A "from" row matches
+    its nearest "to" row (Hamming, lowest index on ties) iff m >= 2 and d1 <= nndr d2; of several "from" rows on one "to" row
+    the smallest distance keeps it, then the lowest "from" row."""
+    r = _nndr(nndr)
+    da, db = [_descriptors(a) for a, _ in pairs], [_descriptors(b) for _, b in pairs]
+    with gpu(device) as (lib, dev):
+        import torch
+        if not pairs:
+            return []
+        n = len(pairs)
+        a_off, b_off = offsets([len(a) for a in da]), offsets([len(b) for b in db])
+        t_a, t_b, t_ao, t_bo = to_dev(_cat(da, 32, np.uint8), dev), to_dev(_cat(db, 32, np.uint8), dev), to_dev(a_off, dev), to_dev(b_off, dev)
+        t_rows = torch.zeros((max(int(a_off[-1]), 1), 2), dtype=torch.int32, device=dev)
+        t_cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+        _lib.check(lib.cslam_vis_match_dev(t_a.data_ptr(), t_ao.data_ptr(), t_b.data_ptr(), t_bo.data_ptr(), n, VIS_DESC_BYTES, r,
+                                           t_rows.data_ptr(), t_cnt.data_ptr(), host(a_off), host(b_off), stream()))
+        rows, cnt = t_rows.cpu().numpy(), t_cnt.cpu().numpy()
+    return [rows[a_off[p]:a_off[p] + cnt[p]].astype(np.int64) for p in range(n)]
+
+
+def match_descriptors(descriptors_from, descriptors_to, nndr=0.8, device=0):
+    return match_descriptors_pairs([(descriptors_from, descriptors_to)], nndr, device)[0]
+
+
+def _point_pairs(pairs):
+    pts, pix = [], []
+    for a, b in pairs:
+        a, b = _rows(a, 3, "points3d"), _rows(b, 2, "pixels")
+        if len(a) != len(b):
+            raise ValueError("a pair is (points3d [M, 3], pixels [M, 2]): %d points, %d pixels" % (len(a), len(b)))
+        pts.append(a)
+        pix.append(b)
+    return pts, pix
+
+
+def pnp_ransac_pairs(pairs, cameras, iterations=300, reproj_error=2.0, min_inliers=20, refine_iterations=10, refine_rounds=2, seed=0,
+                     device=0):
+    """PnP RANSAC of a list of (points3d [M, 3] in the "from" camera frame, pixels [M, 2] in the "to" image), row for row, in
+    ONE call (`cslam_vis_pnp_dev`).  `cameras`: (fx, fy, cx, cy) of the "to" cameras, one for all or one per pair.  Returns a
+    `VisualRegistration` per pair whose `matches` are (k, k)."""
+    it, e, mi, ri, rr, sd = _ransac(iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed)
+    pts, pix = _point_pairs(pairs)
+    cam = _cameras(cameras, len(pairs))
+    with gpu(device) as (lib, dev):
+        if not pairs:
+            return []
+        n = len(pairs)
+        off = offsets([len(a) for a in pts])
+        rows = np.repeat(np.concatenate([np.arange(len(a), dtype=np.int32) for a in pts])[:, None], 2, axis=1)
+        t_pts, t_pix, t_off, t_rows, t_cam = (to_dev(x, dev) for x in (_cat(pts, 3, np.float64), _cat(pix, 2, np.float64), off, rows, cam))
+        t_T, t_info, t_flags = _outputs(n, int(off[-1]), dev)
+        _lib.check(lib.cslam_vis_pnp_dev(t_pts.data_ptr(), t_off.data_ptr(), t_pix.data_ptr(), t_off.data_ptr(), t_rows.data_ptr(),
+                                         t_off.data_ptr(), None, t_cam.data_ptr(), n, it, e, mi, ri, rr, sd, t_T.data_ptr(),
+                                         t_info.data_ptr(), t_flags.data_ptr(), stream()))
+        T, info, flags = t_T.cpu().numpy(), t_info.cpu().numpy(), t_flags.cpu().numpy()
+    return _registrations(T, info, flags, rows, off)
+
+
+Hypotheses = namedtuple("Hypotheses", "R t valid inliers best_hypothesis best_inliers")
+
+
+def hypotheses(pair, camera, iterations=300, reproj_error=2.0, seed=0, device=0):
+    """The staged entry (`cslam_vis_hypotheses_dev`): every hypothesis of one (points3d, pixels) pair.  Returns
+    `Hypotheses`: R [iterations, 3, 3], t [iterations, 3], valid [iterations] bool, inliers [iterations] counts, the best
+    hypothesis and its inlier flags [M]."""
+    it, e, _, _, _, sd = _ransac(iterations, reproj_error, 1, 0, 0, seed)
+    pts, pix = _point_pairs([pair])
+    cam = _cameras(camera, 1)
+    with gpu(device) as (lib, dev):
+        import torch
+        off = offsets([len(pts[0])])
+        t_pts, t_pix, t_off, t_cam = (to_dev(x, dev) for x in (pts[0], pix[0], off, cam))
+        t_T, t_info, t_flags = _outputs(1, int(off[-1]), dev)
+        t_pose = torch.zeros((it, 12), dtype=torch.float64, device=dev)
+        t_hi = torch.zeros((it, 2), dtype=torch.int32, device=dev)
+        _lib.check(lib.cslam_vis_hypotheses_dev(t_pts.data_ptr(), t_pix.data_ptr(), t_off.data_ptr(), t_cam.data_ptr(), 1, it, e, sd,
+                                                t_pose.data_ptr(), t_hi.data_ptr(), t_T.data_ptr(), t_info.data_ptr(),
+                                                t_flags.data_ptr(), host(off), stream()))
+        pose, hi, info, flags = t_pose.cpu().numpy(), t_hi.cpu().numpy(), t_info.cpu().numpy(), t_flags.cpu().numpy()
+    return Hypotheses(pose[:, :9].reshape(it, 3, 3).copy(), pose[:, 9:].copy(), hi[:, 0].astype(bool), hi[:, 1].astype(np.int64),
+                      int(info[0, 5]), flags[:int(off[-1])].astype(bool))
+
+
+def register_pairs(pairs_of_keyframes, cameras, nndr=0.8, iterations=300, reproj_error=2.0, min_inliers=20, refine_iterations=10,
+                   refine_rounds=2, seed=0, device=0):
+    """Matching and PnP RANSAC of a list of (keyframe_from, keyframe_to) in ONE call (`cslam_vis_register_dev`), chained on
+    the device with no host wait between them: the matches select 3D points of "from" and pixels of "to".  Returns a
+    `VisualRegistration` per pair."""
+    r = _nndr(nndr)
+    it, e, mi, ri, rr, sd = _ransac(iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed)
+    kfs = [(_keyframe(a), _keyframe(b)) for a, b in pairs_of_keyframes]
+    cam = _cameras(cameras, len(kfs))
+    with gpu(device) as (lib, dev):
+        import torch
+        if not kfs:
+            return []
+        n = len(kfs)
+        a_off, b_off = offsets([len(a[0]) for a, _ in kfs]), offsets([len(b[0]) for _, b in kfs])
+        t_da = to_dev(_cat([a[2] for a, _ in kfs], 32, np.uint8), dev)
+        t_db = to_dev(_cat([b[2] for _, b in kfs], 32, np.uint8), dev)
+        t_pts = to_dev(_cat([a[1] for a, _ in kfs], 3, np.float64), dev)
+        t_pix = to_dev(_cat([b[0] for _, b in kfs], 2, np.float64), dev)
+        t_ao, t_bo, t_cam = to_dev(a_off, dev), to_dev(b_off, dev), to_dev(cam, dev)
+        t_rows = torch.zeros((max(int(a_off[-1]), 1), 2), dtype=torch.int32, device=dev)
+        t_cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+        t_T, t_info, t_flags = _outputs(n, int(a_off[-1]), dev)
+        _lib.check(lib.cslam_vis_register_dev(t_da.data_ptr(), t_pts.data_ptr(), t_ao.data_ptr(), t_db.data_ptr(), t_pix.data_ptr(),
+                                              t_bo.data_ptr(), t_cam.data_ptr(), n, VIS_DESC_BYTES, r, it, e, mi, ri, rr, sd,
+                                              t_rows.data_ptr(), t_cnt.data_ptr(), t_T.data_ptr(), t_info.data_ptr(), t_flags.data_ptr(),
+                                              host(a_off), host(b_off), stream()))
+        T, info, flags, rows = t_T.cpu().numpy(), t_info.cpu().numpy(), t_flags.cpu().numpy(), t_rows.cpu().numpy()
+    return _registrations(T, info, flags, rows, a_off)
+
+
+def compute_transformation(kf_from, kf_to, camera, **kwargs):
+    """The one-pair form of `register_pairs`: what `registration_.computeTransformation(from, to, ...)` answers."""
+    return register_pairs([(kf_from, kf_to)], camera, **kwargs)[0]

@@ -647,6 +647,55 @@ int cslam_robust_fit_dev(const double *d_src, const int64_t *d_src_off, const do
                          int64_t node_budget, double *d_T, int64_t *d_info, int32_t *d_clique, const int64_t *h_row_off,
                          const int32_t *h_count, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Visual loop closures: geometric verification of a candidate keyframe pair (csrc/vis.hip, csrc/pnp.h).
+ * Replaces the `registration_.computeTransformation(from, to, ...)` calls of src/front_end/rgbd_handler.cpp:433-469
+ * (receive_local_keyframe_match, intra-robot) and :493-554 (receive_local_image_descriptors, inter-robot) on keyframes
+ * that carry 2D keypoints, their 3D points and their descriptors (:471-491), with frontend.pnp_min_inliers = 20
+ * (map_manager_node.cpp:18, rgbd_handler.cpp:72,115-117); stereo_handler.cpp shares the path.  Behind that call is rtabmap's
+ * visual registration, taken here at its defaults as nearest-neighbour matching of binary descriptors with a ratio test and
+ * 3D -> 2D PnP inside RANSAC (300 iterations, 2 px, refinement on the inliers).  rtabmap and OpenCV are third party and
+ * were not available: parity with them is unpinned; tests/vis_reference.py is the float64 yardstick of what is stated here.
+ *
+ * Convention: T maps points of the "from" camera frame into the "to" camera frame; the 3D points come from "from", the
+ * pixels and the intrinsics (fx, fy, cx, cy: pinhole, rectified, no distortion) from "to".  Arrays of a batch are
+ * concatenated with int64 offsets [n_pairs + 1]; all floating arrays are float64.  No float atomics: the same input gives
+ * the same bytes, alone or in any batch. */
+/* cslam_vis_match_dev -- the matching half of computeTransformation (rgbd_handler.cpp:443-445, :519-520).  Descriptors uint8 [n, 32] (desc_bytes must be 32).  Per "from" row the nearest and second-nearest
+ *   "to" row by Hamming distance (the lowest index on ties); the row is a match iff n_to >= 2 and d1 <= nndr d2 (in float64);
+ *   when several "from" rows claim one "to" row the smallest distance keeps it, then the lowest "from" row.
+ *   d_rows [total from, 2] int32 (from row, to row; pair-local) at the pair's "from" offset, ascending in the from row;
+ *   d_count [n_pairs] their number.  h_from_off / h_to_off: the offsets on the host (required; they size the launch). */
+int cslam_vis_match_dev(const uint8_t *d_desc_from, const int64_t *d_from_off, const uint8_t *d_desc_to, const int64_t *d_to_off,
+                        int n_pairs, int desc_bytes, double nndr, int32_t *d_rows, int32_t *d_count, const int64_t *h_from_off,
+                        const int64_t *h_to_off, void *stream);
+/* cslam_vis_pnp_dev -- the PnP RANSAC half of computeTransformation (rgbd_handler.cpp:443-445, :519-520) with
+ *   frontend.pnp_min_inliers (rgbd_handler.cpp:72,115-117), one workgroup per pair.  Correspondence k of pair p is (d_rows[k][0]: a row
+ *   of its d_points [., 3], d_rows[k][1]: a row of its d_pixels [., 2]), k < d_count[p] (NULL: all rows of d_row_off).  One
+ *   whose row lies outside its arrays or whose point or pixel is not finite (a keypoint without depth) is dropped and
+ *   counted; M usable ones remain, in order.
+ *   Hypothesis h in [0, iterations): four distinct indices from the stateless sampler of pnp.h on (seed, h, M); Lambda Twist
+ *   P3P on the first three; of its roots the one with the smallest reprojection error of the fourth (lowest root on ties);
+ *   its inliers: depth > 0 and squared pixel error <= reproj_error^2.  The best hypothesis has the most inliers, then the
+ *   lowest h; one without a root counts 0.  Then refine_rounds rounds of { Gauss-Newton on the inlier set (left perturbation,
+ *   at most refine_iterations steps, stopping after a step of norm < 1e-10 or on a singular system), recount the inliers }.
+ *   d_T [n_pairs, 16] row-major; d_info [n_pairs, 8] int32: status, correspondences given, usable, dropped, final inliers,
+ *   best h (-1: not attempted), its inliers, Gauss-Newton steps taken; d_flags [total rows] int32: 1 for the final inliers.
+ *   status 3: M above 2048, not attempted, T = identity; else 2: M below max(4, min_inliers), not attempted, T = identity;
+ *   else 0: accepted, final inliers >= min_inliers; 1: rejected, T = the best fit found. */
+int cslam_vis_pnp_dev(const double *d_points, const int64_t *d_points_off, const double *d_pixels, const int64_t *d_pixels_off,
+                      const int32_t *d_rows, const int64_t *d_row_off, const int32_t *d_count, const double *d_cameras, int n_pairs,
+                      int iterations, double reproj_error, int min_inliers, int refine_iterations, int refine_rounds, uint64_t seed,
+                      double *d_T, int32_t *d_info, int32_t *d_flags, void *stream);
+/* cslam_vis_register_dev -- the whole call of rgbd_handler.cpp:443-445 / :519-520: both chained on the stream with no host wait between them: the matches of
+ *   (d_desc_from, d_desc_to) select rows of d_points_from [., 3] and d_pixels_to [., 2]; d_rows / d_count as
+ *   cslam_vis_match_dev writes them, d_T / d_info / d_flags as cslam_vis_pnp_dev (d_flags in the layout of d_rows). */
+int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d_points_from, const int64_t *d_from_off,
+                           const uint8_t *d_desc_to, const double *d_pixels_to, const int64_t *d_to_off, const double *d_cameras,
+                           int n_pairs, int desc_bytes, double nndr, int iterations, double reproj_error, int min_inliers,
+                           int refine_iterations, int refine_rounds, uint64_t seed, int32_t *d_rows, int32_t *d_count, double *d_T,
+                           int32_t *d_info, int32_t *d_flags, const int64_t *h_from_off, const int64_t *h_to_off, void *stream);
+
 /* Winograd F(2x2, 3x3) transforms for the 3x3 / stride 1 / pad 1 convolutions of the extractor backbone
  * (the VGG-16 trunk built at cslam/vpr/netvlad.py:163-171; the reference runs it through torch's direct
  * convolution).  Activations are NHWC float32.  conv(x, g) + bias = output(bmm(input(x), U)) with

@@ -82,6 +82,15 @@ int cslam_debug_last_candidates(cslam_bank_t *bank, int64_t nq, int *nseg, float
 int cslam_ring_schedule_describe(int nqt, int n_rows, int n_xcd, int wpx, int32_t info[6], int32_t *tasks, int64_t tasks_cap,
                                  int32_t *task_off, int32_t *qt_nseg, int32_t *qt_segoff);
 
+/* The hypotheses of cslam_vis_pnp_dev (rgbd_handler.cpp:433-469,493-554; csrc/vis.hip) for tests/test_vis_gpu.py: pair p is
+ * d_points [., 3] and d_pixels [., 2] row for row under d_off (h_off: the same on the host, required).  The kernel is the
+ * product's with min_inliers 1 and no refinement.  d_hyp_pose [n_pairs, iterations, 12] = R row-major then t (zeros for a
+ * hypothesis without a root), d_hyp_info [n_pairs, iterations, 2] int32 = valid, inlier count; d_T / d_info / d_flags as
+ * cslam_vis_pnp_dev: the best hypothesis and its inlier set. */
+int cslam_vis_hypotheses_dev(const double *d_points, const double *d_pixels, const int64_t *d_off, const double *d_cameras,
+                             int n_pairs, int iterations, double reproj_error, uint64_t seed, double *d_hyp_pose,
+                             int32_t *d_hyp_info, double *d_T, int32_t *d_info, int32_t *d_flags, const int64_t *h_off, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

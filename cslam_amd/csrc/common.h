@@ -10,6 +10,7 @@
 #include <vector>
 #include "../../include/cslam_hip.h"
 #include "../../include/cslam_hip_experimental.h"
+#include "ragged.h"
 
 #define CSLAM_API extern "C" __attribute__((visibility("default")))
 
@@ -131,8 +132,43 @@ struct StreamScratch {
     type var;                                                                                  \
     { int _st; var = (type)(scratch).get((dev), (stream), (need), (floor_bytes), &_st); if (!var) return _st; }
 
+// the same on the current device: `char *var` = at least `need` bytes on `stream`
+#define SCRATCH_HERE(var, scratch, stream, need, floor_bytes)                                   \
+    int _dev_##var = 0;                                                                         \
+    HIP_TRY(hipGetDevice(&_dev_##var));                                                         \
+    SCRATCH_GET(var, char *, scratch, _dev_##var, (void *)(stream), need, floor_bytes)
+
+// a layout (ragged.h: a callable of a Carver) sized, fetched and placed: the same function, called twice
+#define SCRATCH_CARVE(scratch, stream, floor_bytes, layout)                                     \
+    {                                                                                           \
+        Carver _size;                                                                           \
+        layout(_size);                                                                          \
+        SCRATCH_HERE(carved, scratch, stream, _size.at, floor_bytes);                            \
+        Carver _place(carved);                                                                  \
+        layout(_place);                                                                         \
+    }
+
 static inline int64_t round_up64(int64_t x, int64_t m) { return (x + m - 1) / m * m; }
 static inline int64_t ceil_div64(int64_t x, int64_t m) { return (x + m - 1) / m; }
+
+// ---- ragged batches (ragged.h) as arguments of an entry point -------------------------------------------------------
+#define BATCH_COUNT_CHECK(n) ARG_CHECK((n) >= 1 && (n) <= 65535, #n " must be in [1, 65535]")
+
+// the shared offsets rule; any_start_msg = the message for a negative start where any start >= 0 is allowed
+static inline int offsets_check(const int64_t *off, int n, RaggedShape *s, const char *any_start_msg = nullptr) {
+    const int e = ragged_measure(off, n, any_start_msg != nullptr, s);
+    ARG_CHECK(e != RAGGED_E_START, any_start_msg ? any_start_msg : "offsets must start at row 0");
+    ARG_CHECK(e != RAGGED_E_DECREASE, "offsets must not decrease");
+    return CSLAM_OK;
+}
+
+// `count` entries of a device array into a host vector, on the stream and with no wait of its own: a caller that needs
+// two arrays queues both and waits once
+template <typename T> static inline int read_back_async(std::vector<T> &h, const T *d, size_t count, hipStream_t st) {
+    h.resize(count);
+    HIP_TRY(hipMemcpyAsync(h.data(), d, count * sizeof(T), hipMemcpyDeviceToHost, st));
+    return CSLAM_OK;
+}
 
 // ---- ranking order shared by every kernel -------------------------------------------
 // rank key of a float64 similarity: NaN ranks first (reference: argsort()[::-1] puts NaN

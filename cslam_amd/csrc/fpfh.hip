@@ -437,48 +437,25 @@ __global__ __launch_bounds__(FM_MUTUAL_BLOCK) void fp_mutual_kernel(const int64_
 // ---- host side ---------------------------------------------------------------------------------
 static StreamScratch g_fpfh_scratch;
 
-static int fp_check_offsets(const int64_t *off, int n, bool may_be_empty) {
-    ARG_CHECK(off[0] == 0, "offsets must start at row 0");
-    for (int c = 0; c < n; ++c) {
-        ARG_CHECK(off[c + 1] >= off[c], "offsets must not decrease");
-        ARG_CHECK(may_be_empty || off[c + 1] > off[c], "every feature array needs at least one row");
-        ARG_CHECK(off[c + 1] - off[c] <= 0x7fffffffll - KNN_CHUNK, "a cloud has more points than an int32 index addresses");
-    }
+// The shared offsets rule and this family's limits.  An entry point checks the caller's host copy before anything touches
+// HIP (fp_host_shape); without one it makes one small read-back and one wait and checks then (fp_read_shape).
+static int fp_host_shape(const int64_t *h_off, int n, bool may_be_empty, RaggedShape *s) {
+    if (!h_off) return CSLAM_OK;
+    int rc = offsets_check(h_off, n, s);
+    if (rc) return rc;
+    ARG_CHECK(may_be_empty || s->smallest > 0, "every feature array needs at least one row");
+    ARG_CHECK(s->largest <= 0x7fffffffll - KNN_CHUNK, "a cloud has more points than an int32 index addresses");
     return CSLAM_OK;
 }
 
-// The offsets on the host: the caller's copy, checked before anything touches HIP, or one small read-back that is checked then.
-struct FpOffsets {
+static int fp_read_shape(const int64_t *h_off, const int64_t *d_off, int n, bool may_be_empty, hipStream_t st, RaggedShape *s) {
+    if (h_off) return CSLAM_OK;
     std::vector<int64_t> own;
-    const int64_t *h = nullptr;
-    int64_t total = 0, largest = 0;
-    void measure(int n) {
-        total = h[n];
-        largest = 0;
-        for (int c = 0; c < n; ++c)
-            if (h[c + 1] - h[c] > largest) largest = h[c + 1] - h[c];
-    }
-    int read(const int64_t *d_off, int n, bool may_be_empty, hipStream_t st) {
-        if (h) return CSLAM_OK;
-        own.resize((size_t)n + 1);
-        HIP_TRY(hipMemcpyAsync(own.data(), d_off, own.size() * 8, hipMemcpyDeviceToHost, st));
-        HIP_TRY(hipStreamSynchronize(st));
-        int rc = fp_check_offsets(own.data(), n, may_be_empty);
-        if (rc) return rc;
-        h = own.data();
-        measure(n);
-        return CSLAM_OK;
-    }
-};
-
-#define FP_HOST_OFFSETS(var, h_off, n, may_be_empty)                                     \
-    FpOffsets var;                                                                       \
-    if (h_off) {                                                                         \
-        int _rc = fp_check_offsets((h_off), (n), (may_be_empty));                        \
-        if (_rc) return _rc;                                                             \
-        var.h = (h_off);                                                                 \
-        var.measure(n);                                                                  \
-    }
+    int rc = read_back_async(own, d_off, (size_t)n + 1, st);
+    if (rc) return rc;
+    HIP_TRY(hipStreamSynchronize(st));
+    return fp_host_shape(own.data(), n, may_be_empty, s);
+}
 
 static int fp_list_checks(const int32_t *d_idx, const int32_t *d_count, int width) {
     ARG_CHECK(d_idx && d_count, "NULL neighbour list");
@@ -490,13 +467,14 @@ CSLAM_API int cslam_knn_radius_dev(const double *d_points, const int64_t *d_offs
                                    int32_t *d_idx, double *d_d2, int32_t *d_count, const int64_t *h_offsets, void *stream) {
     ARG_CHECK(radius > 0.0 && radius < INFINITY, "radius must be positive and finite");
     ARG_CHECK(max_nn >= 1 && max_nn <= KNN_MAX_NN, "max_nn must be in [1, 256]");
-    ARG_CHECK(n_clouds >= 1 && n_clouds <= 65535, "n_clouds must be in [1, 65535]");
+    BATCH_COUNT_CHECK(n_clouds);
     ARG_CHECK(d_points && d_offsets && d_idx && d_d2 && d_count, "NULL argument");
-    FP_HOST_OFFSETS(off, h_offsets, n_clouds, true);
+    RaggedShape off;
+    int rc = fp_host_shape(h_offsets, n_clouds, true, &off);
+    if (rc) return rc;
     PTR_DEVICE(d_points);
     hipStream_t st = (hipStream_t)stream;
-    int rc = off.read(d_offsets, n_clouds, true, st);
-    if (rc) return rc;
+    if ((rc = fp_read_shape(h_offsets, d_offsets, n_clouds, true, st, &off))) return rc;
     if (off.total == 0) return CSLAM_OK;
     hipLaunchKernelGGL(fp_knn_kernel, dim3((unsigned)ceil_div64(off.largest, KNN_BLOCK / 64), (unsigned)n_clouds), dim3(KNN_BLOCK), 0, st,
                        d_points, d_offsets, radius * radius, max_nn, d_idx, d_d2, d_count);
@@ -509,7 +487,7 @@ CSLAM_API int cslam_normals_dev(const double *d_points, const int64_t *d_offsets
                                 const double *viewpoint, double *d_normals, const int64_t *h_offsets, void *stream) {
     ARG_CHECK(radius > 0.0 && radius < INFINITY, "radius must be positive and finite");
     ARG_CHECK(max_nn >= 1, "max_nn must be at least 1");
-    ARG_CHECK(n_clouds >= 1 && n_clouds <= 65535, "n_clouds must be in [1, 65535]");
+    BATCH_COUNT_CHECK(n_clouds);
     ARG_CHECK(d_points && d_offsets && d_d2 && d_normals, "NULL argument");
     int rc = fp_list_checks(d_idx, d_count, list_width);
     if (rc) return rc;
@@ -519,10 +497,11 @@ CSLAM_API int cslam_normals_dev(const double *d_points, const int64_t *d_offsets
             ARG_CHECK(fabs(viewpoint[a]) < INFINITY, "the viewpoint must be finite");
             v[a] = viewpoint[a];
         }
-    FP_HOST_OFFSETS(off, h_offsets, n_clouds, true);
+    RaggedShape off;
+    if ((rc = fp_host_shape(h_offsets, n_clouds, true, &off))) return rc;
     PTR_DEVICE(d_points);
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = off.read(d_offsets, n_clouds, true, st))) return rc;
+    if ((rc = fp_read_shape(h_offsets, d_offsets, n_clouds, true, st, &off))) return rc;
     if (off.total == 0) return CSLAM_OK;
     hipLaunchKernelGGL(fp_normals_kernel, dim3((unsigned)ceil_div64(off.total, FPFH_BLOCK)), dim3(FPFH_BLOCK), 0, st, d_points, d_offsets,
                        n_clouds, off.total, d_idx, d_d2, d_count, list_width, radius * radius, max_nn, v[0], v[1], v[2], d_normals);
@@ -533,19 +512,18 @@ CSLAM_API int cslam_normals_dev(const double *d_points, const int64_t *d_offsets
 CSLAM_API int cslam_fpfh_dev(const double *d_points, const double *d_normals, const int64_t *d_offsets, int n_clouds,
                              const int32_t *d_idx, const double *d_d2, const int32_t *d_count, int list_width, double *d_fpfh,
                              double *d_spfh, const int64_t *h_offsets, void *stream) {
-    ARG_CHECK(n_clouds >= 1 && n_clouds <= 65535, "n_clouds must be in [1, 65535]");
+    BATCH_COUNT_CHECK(n_clouds);
     ARG_CHECK(d_points && d_normals && d_offsets && d_d2 && d_fpfh, "NULL argument");
     int rc = fp_list_checks(d_idx, d_count, list_width);
     if (rc) return rc;
-    FP_HOST_OFFSETS(off, h_offsets, n_clouds, true);
+    RaggedShape off;
+    if ((rc = fp_host_shape(h_offsets, n_clouds, true, &off))) return rc;
     PTR_DEVICE(d_points);
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = off.read(d_offsets, n_clouds, true, st))) return rc;
+    if ((rc = fp_read_shape(h_offsets, d_offsets, n_clouds, true, st, &off))) return rc;
     if (off.total == 0) return CSLAM_OK;
     if (!d_spfh) {
-        int dev = 0;
-        HIP_TRY(hipGetDevice(&dev));
-        SCRATCH_GET(base, char *, g_fpfh_scratch, dev, (void *)st, (size_t)off.total * FPFH_BINS * 8, (size_t)1 << 20);
+        SCRATCH_HERE(base, g_fpfh_scratch, st, (size_t)off.total * FPFH_BINS * 8, (size_t)1 << 20);
         d_spfh = (double *)base;
     }
     const unsigned blocks = (unsigned)ceil_div64(off.total, FPFH_BLOCK / 64);
@@ -561,15 +539,15 @@ CSLAM_API int cslam_feature_match_dev(const double *d_a, const int64_t *d_a_off,
                                       int n_pairs, int dim, int32_t *d_nn01, int32_t *d_nn10, int32_t *d_pairs,
                                       int32_t *d_pair_count, const int64_t *h_a_off, const int64_t *h_b_off, void *stream) {
     ARG_CHECK(dim >= 1 && dim <= FM_MAX_DIM, "dim must be in [1, 64]");
-    ARG_CHECK(n_pairs >= 1 && n_pairs <= 65535, "n_pairs must be in [1, 65535]");
+    BATCH_COUNT_CHECK(n_pairs);
     ARG_CHECK(d_a && d_a_off && d_b && d_b_off && d_nn01 && d_nn10, "NULL argument");
     ARG_CHECK((d_pairs == nullptr) == (d_pair_count == nullptr), "d_pairs and d_pair_count go together");
-    FP_HOST_OFFSETS(oa, h_a_off, n_pairs, false);
-    FP_HOST_OFFSETS(ob, h_b_off, n_pairs, false);
+    RaggedShape oa, ob;
+    int rc;
+    if ((rc = fp_host_shape(h_a_off, n_pairs, false, &oa)) || (rc = fp_host_shape(h_b_off, n_pairs, false, &ob))) return rc;
     PTR_DEVICE(d_a);
     hipStream_t st = (hipStream_t)stream;
-    int rc;
-    if ((rc = oa.read(d_a_off, n_pairs, false, st)) || (rc = ob.read(d_b_off, n_pairs, false, st))) return rc;
+    if ((rc = fp_read_shape(h_a_off, d_a_off, n_pairs, false, st, &oa)) || (rc = fp_read_shape(h_b_off, d_b_off, n_pairs, false, st, &ob))) return rc;
     const size_t lds = (size_t)(FM_BLOCK + FM_CHUNK) * dim * sizeof(double);      // 48 KiB at dim 64
     const int64_t largest = oa.largest > ob.largest ? oa.largest : ob.largest;
     const int64_t qblocks = ceil_div64(largest, FM_BLOCK), chunks = ceil_div64(largest, FM_CHUNK);
@@ -578,13 +556,11 @@ CSLAM_API int cslam_feature_match_dev(const double *d_a, const int64_t *d_a_off,
     int64_t lanes = ceil_div64(want, 2 * qblocks * n_pairs);
     lanes = lanes > FM_MAX_LANES ? FM_MAX_LANES : lanes;
     lanes = lanes > chunks ? chunks : lanes;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     const size_t n_part = (size_t)lanes * (size_t)(oa.total + ob.total);
-    const size_t b_d = (size_t)round_up64((int64_t)n_part * 8, 256);
-    SCRATCH_GET(base, char *, g_fpfh_scratch, dev, (void *)st, b_d + n_part * 4, (size_t)1 << 20);
-    double *part_d = (double *)base;
-    int *part_i = (int *)(base + b_d);
+    double *part_d;
+    int *part_i;
+    auto layout = [&](Carver &cv) { part_d = cv.take<double>(n_part); part_i = cv.take<int>(n_part); };
+    SCRATCH_CARVE(g_fpfh_scratch, st, (size_t)1 << 20, layout);
     hipLaunchKernelGGL(fp_match_kernel, dim3((unsigned)qblocks, (unsigned)n_pairs, (unsigned)(2 * lanes)), dim3(FM_BLOCK), lds, st, d_a,
                        d_a_off, d_b, d_b_off, dim, oa.total, ob.total, (int)lanes, part_d, part_i);
     hipLaunchKernelGGL(fp_match_merge_kernel, dim3((unsigned)ceil_div64(oa.total + ob.total, 256)), dim3(256), 0, st, d_a_off, d_b_off,

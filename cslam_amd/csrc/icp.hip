@@ -236,25 +236,23 @@ struct IcpShape {
     int src_blocks, lanes;
 };
 
-// offsets come from device memory: one small copy, then every size is checked before anything is launched
+// offsets come from device memory: both arrays in one wait, then every size is checked before anything is launched
 static int icp_read_shape(const int64_t *d_src_off, const int64_t *d_dst_off, int n_pairs, hipStream_t st, IcpShape *sh) {
-    std::vector<int64_t> so((size_t)n_pairs + 1), dofs((size_t)n_pairs + 1);
-    HIP_TRY(hipMemcpyAsync(so.data(), d_src_off, so.size() * 8, hipMemcpyDeviceToHost, st));
-    HIP_TRY(hipMemcpyAsync(dofs.data(), d_dst_off, dofs.size() * 8, hipMemcpyDeviceToHost, st));
+    std::vector<int64_t> so, dofs;
+    int rc;
+    if ((rc = read_back_async(so, d_src_off, (size_t)n_pairs + 1, st)) || (rc = read_back_async(dofs, d_dst_off, (size_t)n_pairs + 1, st)))
+        return rc;
     HIP_TRY(hipStreamSynchronize(st));
-    ARG_CHECK(so[0] >= 0 && dofs[0] >= 0, "offsets must start at a row >= 0");
-    int64_t max_ns = 0, max_nd = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        const int64_t ns = so[p + 1] - so[p], nd = dofs[p + 1] - dofs[p];
-        ARG_CHECK(ns >= 1 && nd >= 1, "offsets must increase: every source and target cloud needs at least one point");
-        ARG_CHECK(nd <= 0x7fffffffll - ICP_CHUNK, "a target cloud has more points than an int32 index addresses");
-        ARG_CHECK(ns <= (int64_t)ICP_BLOCK * 0x7fffffffll, "a source cloud is too large");
-        if (ns > max_ns) max_ns = ns;
-        if (nd > max_nd) max_nd = nd;
-    }
-    sh->total_src = so[n_pairs];
-    sh->src_blocks = (int)ceil_div64(max_ns, ICP_BLOCK);
-    const int64_t chunks = ceil_div64(max_nd, ICP_CHUNK);
+    RaggedShape src, dst;
+    if ((rc = offsets_check(so.data(), n_pairs, &src, "offsets must start at a row >= 0")) ||
+        (rc = offsets_check(dofs.data(), n_pairs, &dst, "offsets must start at a row >= 0")))
+        return rc;
+    ARG_CHECK(src.smallest >= 1 && dst.smallest >= 1, "offsets must increase: every source and target cloud needs at least one point");
+    ARG_CHECK(dst.largest <= 0x7fffffffll - ICP_CHUNK, "a target cloud has more points than an int32 index addresses");
+    ARG_CHECK(src.largest <= (int64_t)ICP_BLOCK * 0x7fffffffll, "a source cloud is too large");
+    sh->total_src = src.total;
+    sh->src_blocks = (int)ceil_div64(src.largest, ICP_BLOCK);
+    const int64_t chunks = ceil_div64(dst.largest, ICP_CHUNK);
     sh->lanes = (int)(chunks < ICP_MAX_LANES ? chunks : ICP_MAX_LANES);
     return CSLAM_OK;
 }
@@ -268,23 +266,20 @@ static StreamScratch g_icp_scratch;
 
 static int icp_scratch(const IcpShape &sh, int n_pairs, int nsum, hipStream_t st, IcpScratch *ws) {
     const size_t n_part = (size_t)sh.lanes * (size_t)sh.total_src;
-    const size_t b_d2 = round_up64((int64_t)(n_part * 8), 256), b_idx = round_up64((int64_t)(n_part * 4), 256);
-    const size_t b_sums = round_up64((int64_t)n_pairs * sh.src_blocks * nsum * 8, 256);
-    const size_t b_done = round_up64((int64_t)n_pairs * 4, 256);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    SCRATCH_GET(base, char *, g_icp_scratch, dev, (void *)st, b_d2 + b_idx + b_sums + b_done, (size_t)1 << 20);
-    ws->part_d2 = (double *)base;
-    ws->bsums = (double *)(base + b_d2);
-    ws->part_idx = (int *)(base + b_d2 + b_sums);
-    ws->done = (int *)(base + b_d2 + b_sums + b_idx);
+    auto layout = [&](Carver &cv) {
+        ws->part_d2 = cv.take<double>(n_part);
+        ws->bsums = cv.take<double>((size_t)n_pairs * sh.src_blocks * nsum);
+        ws->part_idx = cv.take<int>(n_part);
+        ws->done = cv.take<int>((size_t)n_pairs);
+    };
+    SCRATCH_CARVE(g_icp_scratch, st, (size_t)1 << 20, layout);
     return CSLAM_OK;
 }
 
 static int icp_common_checks(const double *d_src, const int64_t *d_src_off, const double *d_dst, const int64_t *d_dst_off,
                              int n_pairs) {
     ARG_CHECK(d_src && d_src_off && d_dst && d_dst_off, "NULL argument");
-    ARG_CHECK(n_pairs >= 1 && n_pairs <= 65535, "n_pairs must be in [1, 65535]");
+    BATCH_COUNT_CHECK(n_pairs);
     return CSLAM_OK;
 }
 

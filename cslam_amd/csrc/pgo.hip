@@ -561,12 +561,6 @@ struct PgoWs {
 } g_pgo;
 std::mutex g_pgo_mu;
 
-template <class T> T *pgo_take(char *base, size_t *off, size_t count) {
-    T *r = (T *)(base + *off);
-    *off += (count * sizeof(T) + 255) & ~(size_t)255;
-    return r;
-}
-
 int pgo_set_plan(int64_t n, int64_t nf, const int32_t *h_ei, const int32_t *h_ej, int64_t prior, hipStream_t st) {
     PgoWs &w = g_pgo;
     w.planned = false;
@@ -592,30 +586,34 @@ int pgo_set_plan(int64_t n, int64_t nf, const int32_t *h_ei, const int32_t *h_ej
                       {&w.seg_b, &p.seg_b}, {&w.seg_first, &p.seg_first}, {&w.slot_pose, &p.slot_pose}, {&w.slot_link, &p.slot_link},
                       {&w.pose_slot, &p.pose_slot}, {&w.slot_seg, &slot_seg}, {&w.jj_pair, &p.jj_pair}, {&w.tgt_r, &p.tgt_r},
                       {&w.tgt_c, &p.tgt_c}, {&w.tgt_ptr, &p.tgt_ptr}, {&w.tgt_ent, &p.tgt_ent}, {&w.status, &vstatus}};
-    size_t ibytes = 0;
-    for (const Up &u : ups) ibytes += (u.src->size() * 4 + 255 + 256) & ~(size_t)255;
-    std::vector<char> stage(ibytes, 0);
-    int rc = w.ints.ensure(ibytes);
+    auto ints_layout = [&](Carver &cv) {
+        for (const Up &u : ups) *u.dst = cv.take<int32_t>(u.src->size(), 256);
+    };
+    Carver isize;
+    ints_layout(isize);
+    std::vector<char> stage(isize.at, 0);
+    int rc = w.ints.ensure(isize.at);
     if (rc) return rc;
-    size_t off = 0;
-    for (const Up &u : ups) {
-        *u.dst = (int32_t *)((char *)w.ints.p + off);
-        if (!u.src->empty()) memcpy(stage.data() + off, u.src->data(), u.src->size() * 4);
-        off += (u.src->size() * 4 + 255 + 256) & ~(size_t)255;
-    }
-    HIP_TRY(hipMemcpyAsync(w.ints.p, stage.data(), ibytes, hipMemcpyHostToDevice, st));
+    Carver iplace(w.ints.p);
+    ints_layout(iplace);
+    for (const Up &u : ups)
+        if (!u.src->empty()) memcpy(stage.data() + ((char *)*u.dst - (char *)w.ints.p), u.src->data(), u.src->size() * 4);
+    HIP_TRY(hipMemcpyAsync(w.ints.p, stage.data(), isize.at, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));                                      // `stage` leaves scope
     const int64_t nfac = nf + 1, nsum = ceil_div64(std::max(nfac, n), PGO_SUM_BLOCK);
     const size_t counts[] = {(size_t)nfac * PGO_FAC_STRIDE, (size_t)n * 36, (size_t)n * 6, (size_t)std::max<int64_t>(P, 1) * 36, (size_t)nfac,
                              (size_t)std::max<int64_t>(M, 1) * PGO_Y_COLS * 6, (size_t)std::max<int64_t>(S, 1) * PGO_CON_STRIDE, (size_t)N,
                              (size_t)n * 6, (size_t)n, (size_t)nsum, 4};
-    size_t dbytes = 0;
-    for (size_t c : counts) dbytes += (c * 8 + 255) & ~(size_t)255;
-    rc = w.dbl.ensure(dbytes);
-    if (rc) return rc;
     double **views[] = {&w.F, &w.Hdiag, &w.g, &w.Hoff, &w.E, &w.Y, &w.con, &w.rhs, &w.delta, &w.q, &w.partial, &w.scalar};
-    off = 0;
-    for (int k = 0; k < 12; ++k) *views[k] = pgo_take<double>((char *)w.dbl.p, &off, counts[k]);
+    auto dbl_layout = [&](Carver &cv) {
+        for (int k = 0; k < 12; ++k) *views[k] = cv.take<double>(counts[k]);
+    };
+    Carver dsize;
+    dbl_layout(dsize);
+    rc = w.dbl.ensure(dsize.at);
+    if (rc) return rc;
+    Carver dplace(w.dbl.p);
+    dbl_layout(dplace);
     rc = w.dense.ensure((size_t)N * N * 8);
     if (rc) return rc;
     w.planned = true;

@@ -696,54 +696,51 @@ __global__ void rb_assemble_kernel(const int64_t *__restrict__ off, const int32_
 // ---- host side -------------------------------------------------------------------------------------------------------
 static StreamScratch g_robust_scratch;
 
-// Offsets and counts on the host: the caller's copies, checked before anything touches HIP, or one read-back of both.
+// the shared offsets rule and the one limit of this family
+static int rb_shape(const int64_t *off, int n_pairs, RaggedShape *s) {
+    int rc = offsets_check(off, n_pairs, s);
+    if (rc) return rc;
+    ARG_CHECK(s->total <= 0x7fffffffll / 8, "too many correspondence rows in one call");
+    return CSLAM_OK;
+}
+
+// what the caller's host copies allow to check before anything touches HIP
+static int rb_host_checks(const int64_t *h_off, const int32_t *h_count, int n_pairs) {
+    if (!h_off) return CSLAM_OK;
+    RaggedShape s;
+    int rc = rb_shape(h_off, n_pairs, &s);
+    if (rc) return rc;
+    for (int p = 0; h_count && p < n_pairs; ++p)
+        ARG_CHECK(h_count[p] >= 0 && h_count[p] <= h_off[p + 1] - h_off[p], "a count is negative or beyond its pair's rows");
+    return CSLAM_OK;
+}
+
 struct RbPlan {
-    std::vector<int64_t> off;
     std::vector<int32_t> cnt;                              // the counts that are used: cut to the capacity, 0 above the cap
     int64_t total = 0, adj_words = 0;
     int max_n = 0;
 };
 
-static int rb_check(const int64_t *off, const int32_t *cnt, int n_pairs) {
-    ARG_CHECK(off[0] == 0, "offsets must start at row 0");
-    for (int p = 0; p < n_pairs; ++p) {
-        ARG_CHECK(off[p + 1] >= off[p], "offsets must not decrease");
-        ARG_CHECK(!cnt || (cnt[p] >= 0 && cnt[p] <= off[p + 1] - off[p]), "a count is negative or beyond its pair's rows");
-    }
-    ARG_CHECK(off[n_pairs] <= 0x7fffffffll / 8, "too many correspondence rows in one call");
-    return CSLAM_OK;
-}
-
-static int rb_plan_host(const int64_t *h_off, const int32_t *h_count, bool has_count, int n_pairs, RbPlan *pl, bool *complete) {
-    *complete = h_off && (h_count || !has_count);
-    if (h_off) {
-        int rc = rb_check(h_off, has_count ? h_count : nullptr, n_pairs);
-        if (rc) return rc;
-    }
-    if (!*complete) return CSLAM_OK;
-    pl->off.assign(h_off, h_off + n_pairs + 1);
-    pl->cnt.resize((size_t)n_pairs);
-    for (int p = 0; p < n_pairs; ++p) pl->cnt[p] = has_count ? h_count[p] : (int32_t)(h_off[p + 1] - h_off[p] > 0x7fffffff ? 0x7fffffff : h_off[p + 1] - h_off[p]);
-    return CSLAM_OK;
-}
-
-static int rb_plan_finish(const int64_t *d_off, const int32_t *d_count, int n_pairs, bool complete, hipStream_t st, RbPlan *pl) {
-    if (!complete) {                                       // the one host wait of a call without host copies
-        pl->off.resize((size_t)n_pairs + 1);
-        pl->cnt.resize((size_t)n_pairs);
-        HIP_TRY(hipMemcpyAsync(pl->off.data(), d_off, pl->off.size() * 8, hipMemcpyDeviceToHost, st));
-        if (d_count) HIP_TRY(hipMemcpyAsync(pl->cnt.data(), d_count, pl->cnt.size() * 4, hipMemcpyDeviceToHost, st));
+// Offsets and counts on the host: the caller's copies, or one read-back of both and the one host wait of such a call.
+static int rb_plan(const int64_t *d_off, const int32_t *d_count, const int64_t *h_off, const int32_t *h_count, int n_pairs,
+                   hipStream_t st, RbPlan *pl) {
+    std::vector<int64_t> own;
+    int rc;
+    if (h_off && (h_count || !d_count)) {
+        if (d_count) pl->cnt.assign(h_count, h_count + n_pairs);
+    } else {
+        if ((rc = read_back_async(own, d_off, (size_t)n_pairs + 1, st))) return rc;
+        if (d_count && (rc = read_back_async(pl->cnt, d_count, (size_t)n_pairs, st))) return rc;
         HIP_TRY(hipStreamSynchronize(st));
-        int rc = rb_check(pl->off.data(), nullptr, n_pairs);
-        if (rc) return rc;
-        if (!d_count)
-            for (int p = 0; p < n_pairs; ++p) pl->cnt[p] = (int32_t)(pl->off[p + 1] - pl->off[p]);
+        h_off = own.data();
     }
-    pl->total = pl->off[n_pairs];
-    pl->adj_words = 0;
-    pl->max_n = 0;
+    RaggedShape s;
+    if ((rc = rb_shape(h_off, n_pairs, &s))) return rc;
+    pl->total = s.total;
+    pl->cnt.resize((size_t)n_pairs);
     for (int p = 0; p < n_pairs; ++p) {
-        int64_t n = pl->cnt[p], cap = pl->off[p + 1] - pl->off[p];
+        const int64_t cap = h_off[p + 1] - h_off[p];
+        int64_t n = d_count ? pl->cnt[p] : cap;
         n = n < 0 ? 0 : (n > cap ? cap : n);
         n = n > ROBUST_MAX_N ? 0 : n;
         pl->cnt[p] = (int32_t)n;
@@ -754,30 +751,20 @@ static int rb_plan_finish(const int64_t *d_off, const int32_t *d_count, int n_pa
 }
 
 #define RB_PLAN(pl, d_off, d_count, h_off, h_count, n_pairs, first_ptr)                                   \
-    RbPlan pl;                                                                                            \
-    bool _complete;                                                                                       \
     {                                                                                                     \
-        int _rc = rb_plan_host((h_off), (h_count), (d_count) != nullptr, (n_pairs), &pl, &_complete);     \
+        int _rc = rb_host_checks((h_off), (d_count) ? (h_count) : nullptr, (n_pairs));                    \
         if (_rc) return _rc;                                                                              \
     }                                                                                                     \
     PTR_DEVICE(first_ptr);                                                                                \
     hipStream_t st = (hipStream_t)stream;                                                                 \
+    RbPlan pl;                                                                                            \
     {                                                                                                     \
-        int _rc = rb_plan_finish((d_off), (d_count), (n_pairs), _complete, st, &pl);                      \
+        int _rc = rb_plan((d_off), (d_count), (h_off), (h_count), (n_pairs), st, &pl);                    \
         if (_rc) return _rc;                                                                              \
     }
 
-// a carver of one scratch block
-struct RbCarve {
-    char *base;
-    size_t at = 0;
-    explicit RbCarve(char *b) : base(b) {}
-    template <typename T> T *take(size_t n) {
-        T *r = base ? (T *)(base + at) : nullptr;
-        at += (size_t)round_up64((int64_t)(n * sizeof(T)) + 8, 256);
-        return r;
-    }
-};
+// a piece of this family's scratch: 8 bytes of slack behind each
+template <typename T> static T *rb_take(Carver &cv, size_t n) { return cv.take<T>(n, 8); }
 
 struct RbCliqueWs {
     int32_t *core_sorted, *ord, *greedy, *wbest;
@@ -787,7 +774,7 @@ struct RbCliqueWs {
     int64_t stack_words;
 };
 
-static void rb_clique_carve(RbCarve &cv, const RbPlan &pl, int n_pairs, RbCliqueWs *ws) {
+static void rb_clique_carve(Carver &cv, const RbPlan &pl, int n_pairs, RbCliqueWs *ws) {
     const int max_w = (pl.max_n + 63) / 64;
     ws->wl = max_w < 64 ? (max_w > 0 ? max_w : 1) : 64;
     ws->halves = max_w > 64 ? 2 : 1;
@@ -802,14 +789,14 @@ static void rb_clique_carve(RbCarve &cv, const RbPlan &pl, int n_pairs, RbClique
     slots = slots > pl.max_n ? (pl.max_n > 0 ? pl.max_n : 1) : slots;
     ws->slots = (int)slots;
     const size_t waves = (size_t)slots * n_pairs;
-    ws->core_sorted = cv.take<int32_t>((size_t)pl.total);
-    ws->ord = cv.take<int32_t>((size_t)pl.total);
-    ws->greedy = cv.take<int32_t>((size_t)pl.total);
-    ws->adjp = cv.take<u64>((size_t)pl.adj_words);
-    ws->state = cv.take<RbState>((size_t)n_pairs);
-    ws->stack = cv.take<u64>(waves * (size_t)ws->stack_words);
-    ws->wbest = cv.take<int32_t>(waves * (RB_STACK_DEPTH + 1));
-    ws->wkey = cv.take<u64>(waves);
+    ws->core_sorted = rb_take<int32_t>(cv, (size_t)pl.total);
+    ws->ord = rb_take<int32_t>(cv, (size_t)pl.total);
+    ws->greedy = rb_take<int32_t>(cv, (size_t)pl.total);
+    ws->adjp = rb_take<u64>(cv, (size_t)pl.adj_words);
+    ws->state = rb_take<RbState>(cv, (size_t)n_pairs);
+    ws->stack = rb_take<u64>(cv, waves * (size_t)ws->stack_words);
+    ws->wbest = rb_take<int32_t>(cv, waves * (RB_STACK_DEPTH + 1));
+    ws->wkey = rb_take<u64>(cv, waves);
 }
 
 static void rb_launch_graph(const double *ms, const double *md, const int64_t *d_off, const int32_t *d_count, int n_pairs,
@@ -837,7 +824,7 @@ static void rb_launch_clique(const u64 *adj, const int64_t *adj_off, const int32
 }
 
 static int rb_common_checks(int n_pairs, double noise_bound, bool with_bound) {
-    ARG_CHECK(n_pairs >= 1 && n_pairs <= 65535, "n_pairs must be in [1, 65535]");
+    BATCH_COUNT_CHECK(n_pairs);
     ARG_CHECK(!with_bound || (noise_bound > 0.0 && noise_bound < INFINITY), "noise_bound must be positive and finite");
     return CSLAM_OK;
 }
@@ -863,14 +850,9 @@ CSLAM_API int cslam_robust_clique_dev(const uint64_t *d_adj, const int64_t *d_ad
     ARG_CHECK(node_budget >= 1, "node_budget must be at least 1");
     ARG_CHECK(d_adj && d_adj_off && d_deg && d_off && d_clique && d_clique_size && d_certified, "NULL argument");
     RB_PLAN(pl, d_off, d_count, h_off, h_count, n_pairs, d_adj);
-    RbCarve size(nullptr);
     RbCliqueWs ws;
-    rb_clique_carve(size, pl, n_pairs, &ws);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    SCRATCH_GET(base, char *, g_robust_scratch, dev, (void *)st, size.at, (size_t)1 << 20);
-    RbCarve cv(base);
-    rb_clique_carve(cv, pl, n_pairs, &ws);
+    auto layout = [&](Carver &cv) { rb_clique_carve(cv, pl, n_pairs, &ws); };
+    SCRATCH_CARVE(g_robust_scratch, st, (size_t)1 << 20, layout);
     rb_launch_clique((const u64 *)d_adj, d_adj_off, d_deg, d_off, d_count, n_pairs, pl, ws, node_budget, d_clique, d_clique_size,
                      d_certified, d_nodes, st);
     HIP_TRY(hipGetLastError());
@@ -883,7 +865,7 @@ CSLAM_API int cslam_robust_rotation_dev(const double *d_ms, const double *d_md, 
     int rc = rb_common_checks(n_pairs, noise_bound, true);
     if (rc) return rc;
     ARG_CHECK(d_ms && d_md && d_off && d_clique && d_clique_size && d_R && d_weights && d_iters, "NULL argument");
-    if (h_off && (rc = rb_check(h_off, nullptr, n_pairs))) return rc;
+    if ((rc = rb_host_checks(h_off, nullptr, n_pairs))) return rc;
     PTR_DEVICE(d_ms);
     double nb2 = 4.0 * noise_bound * noise_bound;
     if (nb2 < 1e-16) nb2 = 1e-2;
@@ -900,10 +882,9 @@ CSLAM_API int cslam_robust_translation_dev(const double *d_ms, const double *d_m
     if (rc) return rc;
     ARG_CHECK(d_ms && d_md && d_off && d_clique && d_clique_size && d_R && d_t, "NULL argument");
     RB_PLAN(pl, d_off, (const int32_t *)nullptr, h_off, (const int32_t *)nullptr, n_pairs, d_ms);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    SCRATCH_GET(base, char *, g_robust_scratch, dev, (void *)st, (size_t)pl.total * 9 * 8 + 512, (size_t)1 << 20);
-    double *xs = (double *)base, *sorted = xs + 3 * pl.total;
+    double *xs, *sorted;
+    auto layout = [&](Carver &cv) { xs = cv.take<double>(3 * (size_t)pl.total); sorted = cv.take<double>(6 * (size_t)pl.total, 512); };
+    SCRATCH_CARVE(g_robust_scratch, st, (size_t)1 << 20, layout);
     hipLaunchKernelGGL(rb_translation_kernel, dim3(3, (unsigned)n_pairs), dim3(RB_BLOCK), 0, st, d_ms, d_md, d_off, d_clique,
                        d_clique_size, d_R, noise_bound, pl.total, xs, sorted, d_t, d_set);
     HIP_TRY(hipGetLastError());
@@ -927,24 +908,18 @@ CSLAM_API int cslam_robust_fit_dev(const double *d_src, const int64_t *d_src_off
         int64_t *adj_off, *nodes;
         int32_t *deg, *clique, *clique_size, *certified, *iters;
     } a;
-    auto carve = [&](RbCarve &cv) {
-        a.ms = cv.take<double>(3 * total); a.md = cv.take<double>(3 * total);
-        a.R = cv.take<double>(9 * (size_t)n_pairs); a.tr = cv.take<double>(3 * (size_t)n_pairs);
-        a.weights = cv.take<double>(total); a.xs = cv.take<double>(3 * total); a.sorted = cv.take<double>(6 * total);
-        a.adj = cv.take<u64>((size_t)pl.adj_words);
-        a.adj_off = cv.take<int64_t>((size_t)n_pairs + 1); a.nodes = cv.take<int64_t>((size_t)n_pairs);
-        a.deg = cv.take<int32_t>(total); a.clique = cv.take<int32_t>(total);
-        a.clique_size = cv.take<int32_t>((size_t)n_pairs); a.certified = cv.take<int32_t>((size_t)n_pairs);
-        a.iters = cv.take<int32_t>((size_t)n_pairs);
+    auto carve = [&](Carver &cv) {
+        a.ms = rb_take<double>(cv, 3 * total); a.md = rb_take<double>(cv, 3 * total);
+        a.R = rb_take<double>(cv, 9 * (size_t)n_pairs); a.tr = rb_take<double>(cv, 3 * (size_t)n_pairs);
+        a.weights = rb_take<double>(cv, total); a.xs = rb_take<double>(cv, 3 * total); a.sorted = rb_take<double>(cv, 6 * total);
+        a.adj = rb_take<u64>(cv, (size_t)pl.adj_words);
+        a.adj_off = rb_take<int64_t>(cv, (size_t)n_pairs + 1); a.nodes = rb_take<int64_t>(cv, (size_t)n_pairs);
+        a.deg = rb_take<int32_t>(cv, total); a.clique = rb_take<int32_t>(cv, total);
+        a.clique_size = rb_take<int32_t>(cv, (size_t)n_pairs); a.certified = rb_take<int32_t>(cv, (size_t)n_pairs);
+        a.iters = rb_take<int32_t>(cv, (size_t)n_pairs);
         rb_clique_carve(cv, pl, n_pairs, &ws);
     };
-    RbCarve size(nullptr);
-    carve(size);
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    SCRATCH_GET(base, char *, g_robust_scratch, dev, (void *)st, size.at, (size_t)1 << 20);
-    RbCarve cv(base);
-    carve(cv);
+    SCRATCH_CARVE(g_robust_scratch, st, (size_t)1 << 20, carve);
     int32_t *clique = d_clique ? d_clique : a.clique;
     if (pl.max_n > 0)
         hipLaunchKernelGGL(rb_gather_kernel, dim3((unsigned)ceil_div64(pl.max_n, RB_BLOCK), (unsigned)n_pairs), dim3(RB_BLOCK), 0, st, d_src,

@@ -332,29 +332,25 @@ __global__ void vis_identity_rows_kernel(const int64_t *__restrict__ off, int32_
 // ---- host side -----------------------------------------------------------------------------------------------------
 static StreamScratch g_vis_scratch;
 
-static int vis_check_off(const int64_t *off, int n_pairs, const char *what, int64_t *max_n) {
-    ARG_CHECK(off != nullptr, what);
-    ARG_CHECK(off[0] == 0, "offsets must start at row 0");
-    int64_t mx = 0;
-    for (int p = 0; p < n_pairs; ++p) {
-        ARG_CHECK(off[p + 1] >= off[p], "offsets must not decrease");
-        if (off[p + 1] - off[p] > mx) mx = off[p + 1] - off[p];
-    }
-    ARG_CHECK(off[n_pairs] <= 0x7fffffffll / 16, "too many rows in one call");
-    ARG_CHECK(mx <= (int64_t)65535 * VIS_MATCH_BLOCK, "too many rows in one pair");
-    *max_n = mx;
+// the host copy of the offsets is required here; then the shared rule and this family's limits
+static int vis_shape(const int64_t *h_off, int n_pairs, const char *what, RaggedShape *s) {
+    ARG_CHECK(h_off != nullptr, what);
+    int rc = offsets_check(h_off, n_pairs, s);
+    if (rc) return rc;
+    ARG_CHECK(s->total <= 0x7fffffffll / 16, "too many rows in one call");
+    ARG_CHECK(s->largest <= (int64_t)65535 * VIS_MATCH_BLOCK, "too many rows in one pair");
     return CSLAM_OK;
 }
 
 static int vis_match_checks(int n_pairs, int desc_bytes, double nndr) {
-    ARG_CHECK(n_pairs >= 1 && n_pairs <= 65535, "n_pairs must be in [1, 65535]");
+    BATCH_COUNT_CHECK(n_pairs);
     ARG_CHECK(desc_bytes == VIS_DESC_BYTES, "descriptors must be 32 bytes wide (ORB / BRIEF-32)");
     ARG_CHECK(nndr >= 0.0 && nndr <= 1.0, "nndr must be in [0, 1]");
     return CSLAM_OK;
 }
 
 static int vis_pnp_checks(int n_pairs, int iterations, double reproj_error, int min_inliers, int refine_iterations, int refine_rounds) {
-    ARG_CHECK(n_pairs >= 1 && n_pairs <= 65535, "n_pairs must be in [1, 65535]");
+    BATCH_COUNT_CHECK(n_pairs);
     ARG_CHECK(iterations >= 1 && iterations <= (1 << 24), "iterations must be in [1, 2^24]");
     ARG_CHECK(reproj_error > 0.0 && reproj_error < INFINITY, "reproj_error must be positive and finite");
     ARG_CHECK(min_inliers >= 1, "min_inliers must be at least 1");
@@ -363,16 +359,14 @@ static int vis_pnp_checks(int n_pairs, int iterations, double reproj_error, int 
 }
 
 static int vis_launch_match(const uint8_t *da, const int64_t *a_off, const uint8_t *db, const int64_t *b_off, int n_pairs,
-                            int64_t max_a, int64_t total_a, int64_t total_b, double nndr, int32_t *rows, int32_t *count, hipStream_t st) {
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    const size_t claim_bytes = (size_t)round_up64(total_b * 8 + 8, 256), nn_bytes = (size_t)round_up64(total_a * 8 + 8, 256);
-    SCRATCH_GET(base, char *, g_vis_scratch, dev, (void *)st, claim_bytes + nn_bytes, (size_t)1 << 20);
-    u64 *claim = (u64 *)base;
-    int32_t *nn = (int32_t *)(base + claim_bytes);
-    HIP_TRY(hipMemsetAsync(claim, 0xff, claim_bytes, st));
-    if (max_a > 0)
-        hipLaunchKernelGGL(vis_match_kernel, dim3((unsigned)ceil_div64(max_a, VIS_MATCH_BLOCK), (unsigned)n_pairs), dim3(VIS_MATCH_BLOCK), 0,
+                            const RaggedShape &a, const RaggedShape &b, double nndr, int32_t *rows, int32_t *count, hipStream_t st) {
+    u64 *claim;
+    int32_t *nn;
+    auto layout = [&](Carver &cv) { claim = cv.take<u64>((size_t)b.total, 8); nn = cv.take<int32_t>(2 * (size_t)a.total, 8); };
+    SCRATCH_CARVE(g_vis_scratch, st, (size_t)1 << 20, layout);
+    HIP_TRY(hipMemsetAsync(claim, 0xff, (size_t)((char *)nn - (char *)claim), st));     // the whole piece
+    if (a.largest > 0)
+        hipLaunchKernelGGL(vis_match_kernel, dim3((unsigned)ceil_div64(a.largest, VIS_MATCH_BLOCK), (unsigned)n_pairs), dim3(VIS_MATCH_BLOCK), 0,
                            st, (const uint32_t *)da, a_off, (const uint32_t *)db, b_off, nndr, nn, claim);
     hipLaunchKernelGGL(vis_compact_kernel, dim3((unsigned)n_pairs), dim3(VIS_BLOCK), 0, st, a_off, b_off, nn, claim, rows, count);
     HIP_TRY(hipGetLastError());
@@ -397,12 +391,11 @@ CSLAM_API int cslam_vis_match_dev(const uint8_t *d_desc_from, const int64_t *d_f
     int rc = vis_match_checks(n_pairs, desc_bytes, nndr);
     if (rc) return rc;
     ARG_CHECK(d_desc_from && d_from_off && d_desc_to && d_to_off && d_rows && d_count, "NULL argument");
-    int64_t max_a, max_b;
-    if ((rc = vis_check_off(h_from_off, n_pairs, "h_from_off is required", &max_a))) return rc;
-    if ((rc = vis_check_off(h_to_off, n_pairs, "h_to_off is required", &max_b))) return rc;
+    RaggedShape from, to;
+    if ((rc = vis_shape(h_from_off, n_pairs, "h_from_off is required", &from))) return rc;
+    if ((rc = vis_shape(h_to_off, n_pairs, "h_to_off is required", &to))) return rc;
     PTR_DEVICE(d_desc_from);
-    return vis_launch_match(d_desc_from, d_from_off, d_desc_to, d_to_off, n_pairs, max_a, h_from_off[n_pairs], h_to_off[n_pairs], nndr,
-                            d_rows, d_count, (hipStream_t)stream);
+    return vis_launch_match(d_desc_from, d_from_off, d_desc_to, d_to_off, n_pairs, from, to, nndr, d_rows, d_count, (hipStream_t)stream);
 }
 
 CSLAM_API int cslam_vis_pnp_dev(const double *d_points, const int64_t *d_points_off, const double *d_pixels,
@@ -431,14 +424,12 @@ CSLAM_API int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d
     if ((rc = vis_pnp_checks(n_pairs, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds))) return rc;
     ARG_CHECK(d_desc_from && d_points_from && d_from_off && d_desc_to && d_pixels_to && d_to_off && d_cameras && d_rows && d_count &&
               d_T && d_info && d_flags, "NULL argument");
-    int64_t max_a, max_b;
-    if ((rc = vis_check_off(h_from_off, n_pairs, "h_from_off is required", &max_a))) return rc;
-    if ((rc = vis_check_off(h_to_off, n_pairs, "h_to_off is required", &max_b))) return rc;
+    RaggedShape from, to;
+    if ((rc = vis_shape(h_from_off, n_pairs, "h_from_off is required", &from))) return rc;
+    if ((rc = vis_shape(h_to_off, n_pairs, "h_to_off is required", &to))) return rc;
     PTR_DEVICE(d_desc_from);
     hipStream_t st = (hipStream_t)stream;
-    if ((rc = vis_launch_match(d_desc_from, d_from_off, d_desc_to, d_to_off, n_pairs, max_a, h_from_off[n_pairs], h_to_off[n_pairs], nndr,
-                               d_rows, d_count, st)))
-        return rc;
+    if ((rc = vis_launch_match(d_desc_from, d_from_off, d_desc_to, d_to_off, n_pairs, from, to, nndr, d_rows, d_count, st))) return rc;
     VisPnpArgs a = {d_points_from, d_from_off, d_pixels_to, d_to_off, d_rows, d_from_off, d_count, d_cameras, iterations, min_inliers,
                     refine_iterations, refine_rounds, reproj_error * reproj_error, (u64)seed, d_T, d_info, d_flags, nullptr, nullptr};
     return vis_launch_pnp(a, n_pairs, st);
@@ -451,15 +442,14 @@ CSLAM_API int cslam_vis_hypotheses_dev(const double *d_points, const double *d_p
     int rc = vis_pnp_checks(n_pairs, iterations, reproj_error, 1, 0, 0);
     if (rc) return rc;
     ARG_CHECK(d_points && d_pixels && d_off && d_cameras && d_hyp_pose && d_hyp_info && d_T && d_info && d_flags, "NULL argument");
-    int64_t max_n;
-    if ((rc = vis_check_off(h_off, n_pairs, "h_off is required", &max_n))) return rc;
+    RaggedShape sh;
+    if ((rc = vis_shape(h_off, n_pairs, "h_off is required", &sh))) return rc;
     PTR_DEVICE(d_points);
     hipStream_t st = (hipStream_t)stream;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    SCRATCH_GET(rows, int32_t *, g_vis_scratch, dev, (void *)st, (size_t)h_off[n_pairs] * 8 + 256, (size_t)1 << 20);
-    if (max_n > 0)
-        hipLaunchKernelGGL(vis_identity_rows_kernel, dim3((unsigned)ceil_div64(max_n, 256), (unsigned)n_pairs), dim3(256), 0, st, d_off, rows);
+    SCRATCH_HERE(base, g_vis_scratch, st, (size_t)sh.total * 8 + 256, (size_t)1 << 20);
+    int32_t *rows = (int32_t *)base;
+    if (sh.largest > 0)
+        hipLaunchKernelGGL(vis_identity_rows_kernel, dim3((unsigned)ceil_div64(sh.largest, 256), (unsigned)n_pairs), dim3(256), 0, st, d_off, rows);
     // min_inliers 1: a pair of four correspondences or more is attempted, as the staged tests need
     VisPnpArgs a = {d_points, d_off, d_pixels, d_off, rows, d_off, nullptr, d_cameras, iterations, 1, 0, 0, reproj_error * reproj_error,
                     (u64)seed, d_T, d_info, d_flags, d_hyp_pose, d_hyp_info};

@@ -381,10 +381,11 @@ static void vox_mark(bool on, int k, hipStream_t st) {
     if (on) (void)hipEventRecord(g_vox_prof.ev[k], st);
 }
 
-static int vox_check_offsets(const int64_t *off, int n_clouds) {
-    ARG_CHECK(off[0] == 0, "offsets must start at row 0");
-    for (int c = 0; c < n_clouds; ++c) ARG_CHECK(off[c + 1] >= off[c], "offsets must not decrease");
-    ARG_CHECK(off[n_clouds] <= VOXEL_MAX_POINTS, "more points than an int32 index addresses");
+// the shared offsets rule and the one limit of the sort
+static int vox_shape(const int64_t *off, int n_clouds, RaggedShape *s) {
+    int rc = offsets_check(off, n_clouds, s);
+    if (rc) return rc;
+    ARG_CHECK(s->total <= VOXEL_MAX_POINTS, "more points than an int32 index addresses");
     return CSLAM_OK;
 }
 
@@ -392,15 +393,14 @@ CSLAM_API int cslam_voxel_downsample_dev(const double *d_points, const int64_t *
                                          double *d_out, int64_t *d_out_offsets, int32_t *d_counts, int32_t *d_status,
                                          const int64_t *h_offsets, void *stream) {
     ARG_CHECK(voxel > 0.0 && voxel < INFINITY, "voxel must be positive and finite");
-    ARG_CHECK(n_clouds >= 1 && n_clouds <= 65535, "n_clouds must be in [1, 65535]");
+    BATCH_COUNT_CHECK(n_clouds);
     ARG_CHECK(d_offsets && d_out_offsets && d_status, "NULL argument");
     int rc;
-    if (h_offsets && (rc = vox_check_offsets(h_offsets, n_clouds))) return rc;
-    ARG_CHECK((d_points && d_out) || (h_offsets && h_offsets[n_clouds] == 0), "NULL argument");
+    RaggedShape sh = {};
+    if (h_offsets && (rc = vox_shape(h_offsets, n_clouds, &sh))) return rc;
+    ARG_CHECK((d_points && d_out) || (h_offsets && sh.total == 0), "NULL argument");
     PTR_DEVICE(d_offsets);
     hipStream_t st = (hipStream_t)stream;
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
     bool prof;
     {
         std::lock_guard<std::mutex> lock(g_vox_prof.mu);
@@ -414,12 +414,15 @@ CSLAM_API int cslam_voxel_downsample_dev(const double *d_points, const int64_t *
     // before the wait: bounds and meta, whose launch shape depends on n_clouds alone
     int nb = 2048 / n_clouds;
     nb = nb < 1 ? 1 : (nb > 64 ? 64 : nb);
-    const size_t b_part = (size_t)round_up64((int64_t)n_clouds * nb * VOX_NPART * 8, 256);
-    const size_t b_origin = (size_t)round_up64((int64_t)n_clouds * 3 * 8, 256);
-    const size_t b_meta = (size_t)round_up64((int64_t)n_clouds * 4 * 4, 256);
-    SCRATCH_GET(hbase, char *, g_voxel_head_scratch, dev, (void *)st, b_part + b_origin + b_meta + 256, (size_t)1 << 16);
-    double *part = (double *)hbase, *origin = (double *)(hbase + b_part);
-    int *meta = (int *)(hbase + b_part + b_origin), *head = (int *)(hbase + b_part + b_origin + b_meta);
+    double *part, *origin;
+    int *meta, *head;
+    auto head_layout = [&](Carver &cv) {
+        part = cv.take<double>((size_t)n_clouds * nb * VOX_NPART);
+        origin = cv.take<double>((size_t)n_clouds * 3);
+        meta = cv.take<int>((size_t)n_clouds * 4);
+        head = cv.take<int>(2);                            // 8 bytes in a piece of 256
+    };
+    SCRATCH_CARVE(g_voxel_head_scratch, st, (size_t)1 << 16, head_layout);
     vox_mark(prof, 0, st);
     HIP_TRY(hipMemsetAsync(head, 0, 8, st));
     hipLaunchKernelGGL(vox_bounds_kernel, dim3((unsigned)nb, (unsigned)n_clouds), dim3(VOX_BOUNDS_BLOCK), 0, st, d_points, d_offsets, part);
@@ -429,18 +432,12 @@ CSLAM_API int cslam_voxel_downsample_dev(const double *d_points, const int64_t *
     int h_head[2] = {0, 0};
     std::vector<int64_t> read_off;
     HIP_TRY(hipMemcpyAsync(h_head, head, 8, hipMemcpyDeviceToHost, st));
-    if (!h_offsets) {
-        read_off.resize((size_t)n_clouds + 1);
-        HIP_TRY(hipMemcpyAsync(read_off.data(), d_offsets, read_off.size() * 8, hipMemcpyDeviceToHost, st));
-    }
+    if (!h_offsets && (rc = read_back_async(read_off, d_offsets, (size_t)n_clouds + 1, st))) return rc;
     HIP_TRY(hipStreamSynchronize(st));                     // the one host wait
-    if (!h_offsets) {
-        if ((rc = vox_check_offsets(read_off.data(), n_clouds))) return rc;
-        h_offsets = read_off.data();
-    }
-    const int64_t n = h_offsets[n_clouds];
+    if (!h_offsets && (rc = vox_shape(read_off.data(), n_clouds, &sh))) return rc;
+    const int64_t n = sh.total;
     VoxelPlan pl;
-    if (voxel_make_plan(n, n_clouds, h_head[0], h_head[1], &pl)) {
+    if (voxel_make_plan(n, n_clouds, h_head[0], h_head[1], nullptr, &pl)) {
         cslam_set_error("voxel down-sampling: sizes outside the plan's limits");
         return CSLAM_E_INVALID;
     }
@@ -449,42 +446,35 @@ CSLAM_API int cslam_voxel_downsample_dev(const double *d_points, const int64_t *
         HIP_TRY(hipMemsetAsync(d_out_offsets, 0, ((size_t)n_clouds + 1) * 8, st));
         for (int k = 3; k < VOX_EV; ++k) vox_mark(prof, k, st);
     } else {
-        SCRATCH_GET(base, char *, g_voxel_scratch, dev, (void *)st, pl.bytes, (size_t)1 << 20);
-        uint64_t *keys[2] = {(uint64_t *)(base + pl.o_keys[0]), (uint64_t *)(base + pl.o_keys[1])};
-        uint32_t *idx[2] = {(uint32_t *)(base + pl.o_idx[0]), (uint32_t *)(base + pl.o_idx[1])};
-        uint16_t *cloud_of = (uint16_t *)(base + pl.o_cloud);
-        uint8_t *flags = (uint8_t *)(base + pl.o_flags);
-        uint32_t *rank = (uint32_t *)(base + pl.o_rank), *seg_start = (uint32_t *)(base + pl.o_start);
-        uint32_t *seg_end = (uint32_t *)(base + pl.o_end), *hist = (uint32_t *)(base + pl.o_hist);
-        uint32_t *totals = (uint32_t *)(base + pl.o_totals);
-        uint32_t *tile_count = (uint32_t *)(base + pl.o_tile_count), *rows = (uint32_t *)(base + pl.o_rows);
+        SCRATCH_HERE(base, g_voxel_scratch, st, pl.bytes, (size_t)1 << 20);
+        voxel_make_plan(n, n_clouds, h_head[0], h_head[1], base, &pl);     // the same plan, placed
         hipLaunchKernelGGL(vox_key_kernel, dim3((unsigned)ceil_div64(n, 256)), dim3(256), 0, st, d_points, d_offsets, n_clouds, n, voxel,
-                           origin, meta, pl.invalid_shift, keys[0], idx[0], cloud_of);
+                           origin, meta, pl.invalid_shift, pl.keys[0], pl.idx[0], pl.cloud_of);
         vox_mark(prof, 3, st);
         int cur = 0;
         for (int pass = 0; pass < pl.key_passes + pl.cloud_passes; ++pass) {
             int shift, from_cloud;
             voxel_pass_digit(&pl, pass, &shift, &from_cloud);
-            hipLaunchKernelGGL(vox_hist_kernel, dim3((unsigned)pl.tiles), dim3(VOXEL_SORT_BLOCK), 0, st, keys[cur], idx[cur], cloud_of, n,
-                               shift, from_cloud, hist);
-            hipLaunchKernelGGL(vox_digit_scan_kernel, dim3(256), dim3(VOXEL_SORT_BLOCK), 0, st, hist, pl.tiles, totals);
-            hipLaunchKernelGGL(vox_scatter_kernel, dim3((unsigned)pl.tiles), dim3(VOXEL_SORT_BLOCK), 0, st, keys[cur], idx[cur], cloud_of, n,
-                               shift, from_cloud, hist, totals, keys[cur ^ 1], idx[cur ^ 1]);
+            hipLaunchKernelGGL(vox_hist_kernel, dim3((unsigned)pl.tiles), dim3(VOXEL_SORT_BLOCK), 0, st, pl.keys[cur], pl.idx[cur], pl.cloud_of, n,
+                               shift, from_cloud, pl.hist);
+            hipLaunchKernelGGL(vox_digit_scan_kernel, dim3(256), dim3(VOXEL_SORT_BLOCK), 0, st, pl.hist, pl.tiles, pl.totals);
+            hipLaunchKernelGGL(vox_scatter_kernel, dim3((unsigned)pl.tiles), dim3(VOXEL_SORT_BLOCK), 0, st, pl.keys[cur], pl.idx[cur], pl.cloud_of, n,
+                               shift, from_cloud, pl.hist, pl.totals, pl.keys[cur ^ 1], pl.idx[cur ^ 1]);
             cur ^= 1;
         }
         vox_mark(prof, 4, st);
-        hipLaunchKernelGGL(vox_flag_kernel, dim3((unsigned)pl.flag_tiles), dim3(VOXEL_FLAG_BLOCK), 0, st, keys[cur], cloud_of, n,
-                           pl.invalid_shift, flags, tile_count);
-        hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOXEL_SCAN_BLOCK), 0, st, tile_count, pl.flag_tiles, rows);
-        hipLaunchKernelGGL(vox_rank_kernel, dim3((unsigned)pl.flag_tiles), dim3(VOXEL_FLAG_BLOCK), 0, st, flags, n, tile_count, rank,
-                           seg_start, seg_end);
+        hipLaunchKernelGGL(vox_flag_kernel, dim3((unsigned)pl.flag_tiles), dim3(VOXEL_FLAG_BLOCK), 0, st, pl.keys[cur], pl.cloud_of, n,
+                           pl.invalid_shift, pl.flags, pl.tile_count);
+        hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOXEL_SCAN_BLOCK), 0, st, pl.tile_count, pl.flag_tiles, pl.rows);
+        hipLaunchKernelGGL(vox_rank_kernel, dim3((unsigned)pl.flag_tiles), dim3(VOXEL_FLAG_BLOCK), 0, st, pl.flags, n, pl.tile_count, pl.rank,
+                           pl.seg_start, pl.seg_end);
         hipLaunchKernelGGL(vox_out_offsets_kernel, dim3((unsigned)ceil_div64((int64_t)n_clouds + 1, 256)), dim3(256), 0, st, d_offsets,
-                           n_clouds, n, rank, rows, d_out_offsets);
+                           n_clouds, n, pl.rank, pl.rows, d_out_offsets);
         vox_mark(prof, 5, st);
         const int64_t want = ceil_div64(n, VOXEL_SEG_BLOCK / 64);
         const int64_t cap = (int64_t)(cslam_cu_count() > 0 ? cslam_cu_count() : 256) * 8;
-        hipLaunchKernelGGL(vox_segment_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(VOXEL_SEG_BLOCK), 0, st, d_points, idx[cur],
-                           seg_start, seg_end, rows, d_out, d_counts);
+        hipLaunchKernelGGL(vox_segment_kernel, dim3((unsigned)(want < cap ? want : cap)), dim3(VOXEL_SEG_BLOCK), 0, st, d_points, pl.idx[cur],
+                           pl.seg_start, pl.seg_end, pl.rows, d_out, d_counts);
         vox_mark(prof, 6, st);
     }
     HIP_TRY(hipGetLastError());

@@ -3,6 +3,7 @@
 #pragma once
 #include <stdint.h>
 #include <stddef.h>
+#include "ragged.h"
 
 #define VOXEL_TILE 2048          // keys per workgroup per radix pass (256 threads x 8 keys, a wave owns 512 in a row)
 #define VOXEL_SORT_BLOCK 256     // threads per workgroup of the histogram and scatter kernels
@@ -18,8 +19,12 @@ struct VoxelPlan {
     int key_passes, cloud_passes;
     int invalid_shift;           // position of that bit, -1 when every row of the batch exists
     int64_t n, tiles, flag_tiles;
-    // byte offsets into the scratch, each a multiple of 256
-    size_t o_keys[2], o_idx[2], o_cloud, o_flags, o_rank, o_start, o_end, o_hist, o_totals, o_tile_count, o_rows, bytes;
+    // the pieces of the scratch, each on a multiple of 256 bytes: null from a plan that was made without the block
+    uint64_t *keys[2];
+    uint32_t *idx[2], *rank, *seg_start, *seg_end, *hist, *totals, *tile_count, *rows;
+    uint16_t *cloud_of;
+    uint8_t *flags;
+    size_t bytes;
 };
 
 static inline int voxel_bits_of(uint64_t v) {
@@ -28,15 +33,10 @@ static inline int voxel_bits_of(uint64_t v) {
     return b;
 }
 
-static inline size_t voxel_carve(size_t *at, size_t bytes) {
-    const size_t here = *at;
-    *at = here + (bytes + 255) / 256 * 256;
-    return here;
-}
-
 // n points in n_clouds clouds; max_key_bits = the largest bx + by + bz over the clouds (0 .. 63); any_invalid = some
-// row is non-finite or belongs to a cloud beyond the index range.  Returns 0, or -1 on sizes outside the limits.
-static inline int voxel_make_plan(int64_t n, int n_clouds, int max_key_bits, int any_invalid, VoxelPlan *p) {
+// row is non-finite or belongs to a cloud beyond the index range; base = the scratch block of p->bytes, or null to learn
+// p->bytes.  Returns 0, or -1 on sizes outside the limits.
+static inline int voxel_make_plan(int64_t n, int n_clouds, int max_key_bits, int any_invalid, void *base, VoxelPlan *p) {
     if (n < 0 || n > VOXEL_MAX_POINTS || n_clouds < 1 || n_clouds > 65535) return -1;
     if (max_key_bits < 0 || max_key_bits > 3 * VOXEL_AXIS_BITS) return -1;
     p->n = n;
@@ -46,22 +46,22 @@ static inline int voxel_make_plan(int64_t n, int n_clouds, int max_key_bits, int
     p->cloud_passes = (voxel_bits_of((uint64_t)(n_clouds - 1)) + VOXEL_RADIX_BITS - 1) / VOXEL_RADIX_BITS;
     p->tiles = (n + VOXEL_TILE - 1) / VOXEL_TILE;
     p->flag_tiles = (n + VOXEL_FLAG_BLOCK - 1) / VOXEL_FLAG_BLOCK;
-    size_t at = 0;
+    Carver cv(base);
     const size_t un = (size_t)n;
     for (int k = 0; k < 2; ++k) {
-        p->o_keys[k] = voxel_carve(&at, un * 8);
-        p->o_idx[k] = voxel_carve(&at, un * 4);
+        p->keys[k] = cv.take<uint64_t>(un);
+        p->idx[k] = cv.take<uint32_t>(un);
     }
-    p->o_cloud = voxel_carve(&at, un * 2);
-    p->o_flags = voxel_carve(&at, un);
-    p->o_rank = voxel_carve(&at, un * 4);
-    p->o_start = voxel_carve(&at, un * 4);
-    p->o_end = voxel_carve(&at, un * 4);
-    p->o_hist = voxel_carve(&at, (size_t)p->tiles * (1u << VOXEL_RADIX_BITS) * 4);
-    p->o_totals = voxel_carve(&at, (1u << VOXEL_RADIX_BITS) * 4);
-    p->o_tile_count = voxel_carve(&at, (size_t)p->flag_tiles * 4);
-    p->o_rows = voxel_carve(&at, 4);
-    p->bytes = at;
+    p->cloud_of = cv.take<uint16_t>(un);
+    p->flags = cv.take<uint8_t>(un);
+    p->rank = cv.take<uint32_t>(un);
+    p->seg_start = cv.take<uint32_t>(un);
+    p->seg_end = cv.take<uint32_t>(un);
+    p->hist = cv.take<uint32_t>((size_t)p->tiles << VOXEL_RADIX_BITS);
+    p->totals = cv.take<uint32_t>((size_t)1 << VOXEL_RADIX_BITS);
+    p->tile_count = cv.take<uint32_t>((size_t)p->flag_tiles);
+    p->rows = cv.take<uint32_t>(1);
+    p->bytes = cv.at;
     return 0;
 }
 

@@ -272,3 +272,25 @@ def test_end_to_end_share_of_true_partners(u, scenes):
     share = ref.true_partner_share(idx0, idx1, perm, len(pts))
     print("true partners: %.5f of %d points, %d mutual matches (restatement: at least %.3f)" % (share, len(pts), len(idx0), E2E_SHARE))
     assert share >= E2E_SHARE - 0.01
+
+
+def test_match_scratch_is_carved_afresh_for_every_batch(u):
+    """One stream, so one scratch block: a pair of a few rows (both pieces shorter than 256 bytes), then three larger pairs
+    with a one-row member, then the small pair again.  Both small results equal, byte for byte, the one computed before
+    anything else here."""
+    import torch
+    rng = np.random.default_rng(41)
+    small = [(rng.standard_normal((9, 33)), rng.standard_normal((7, 33)))]
+    large = [(rng.standard_normal((300, 33)), rng.standard_normal((411, 33))), (rng.standard_normal((1, 33)), rng.standard_normal((1, 33))),
+             (rng.standard_normal((257, 33)), rng.standard_normal((500, 33)))]
+
+    def raw(pairs):
+        both = u.find_correspondences_pairs(pairs) + u.find_correspondences_pairs(pairs, mutual_filter=False)
+        return b"".join(i0.tobytes() + i1.tobytes() for i0, i1 in both)
+
+    first = raw(small)
+    with torch.cuda.stream(torch.cuda.Stream()):
+        runs = [raw(small), raw(large), raw(small)]
+    assert runs[0] == first and runs[2] == first and runs[1] == raw(large)
+    (i0, i1), (w0, w1) = u.find_correspondences_pairs(small)[0], ref.find_correspondences(*small[0])
+    assert np.array_equal(i0, w0) and np.array_equal(i1, w1)

@@ -266,3 +266,29 @@ def test_typed_errors(icp):
     assert lib.cslam_icp_correspondences_dev(*args, 2, None, 1.0, idx.data_ptr(), d2.data_ptr(), None) == 0
     torch.cuda.synchronize()
     assert idx.cpu().tolist() == list(range(20)) * 2                              # each pair: a cloud against itself
+
+
+def test_scratch_is_carved_afresh_for_every_batch(icp):
+    """One stream, so one scratch block: a pair of a few rows (every piece shorter than 256 bytes), then three larger pairs
+    with a one-point member, then the small pair again.  The block keeps what the larger batch wrote and is cut differently
+    each time; both small results equal, byte for byte, the one computed before anything else here."""
+    import torch
+    rng = np.random.default_rng(31)
+    T = ref.Rt2T(Rotation.from_rotvec([0.02, -0.03, 0.05]).as_matrix(), np.array([0.1, -0.05, 0.02]))
+
+    def pair(ns, nd):
+        src = rng.uniform(-3.0, 3.0, (max(ns, nd), 3))
+        return src[:ns], ref.apply_T_fma(T, src)[:nd]
+
+    small, large = [pair(23, 37)], [pair(300, 411), pair(1, 1), pair(257, 500)]
+    stages = ((4.0, 3), (1.0, 2))
+
+    def raw(pairs):
+        return b"".join(r.transformation.tobytes() + np.array([r.fitness, r.inlier_rmse]).tobytes() + bytes([r.iterations])
+                        + r.correspondences.to_bytes(4, "little") for r in icp.register_pairs(pairs, VOXEL, None, stages))
+
+    first = raw(small)
+    with torch.cuda.stream(torch.cuda.Stream()):
+        runs = [raw(small), raw(large), raw(small)]
+    assert runs[0] == first and runs[2] == first
+    assert runs[1] == raw(large) and len(runs[1]) == 3 * len(first)

@@ -266,3 +266,22 @@ def test_compute_transform_at_its_defaults_is_unchanged(u):
                                                                                staged.correspondences, staged.iterations)
     golden = ref.golden("compute_transform_default_street1.npy")
     assert golden is not None and ok.transformation.tobytes() == golden.tobytes()     # the parent commit's bytes
+
+
+def test_fit_scratch_is_carved_afresh_for_every_batch(u):
+    """One stream, so one scratch block of 23 pieces: a pair of 30 matches (most pieces shorter than 256 bytes), then three
+    larger pairs with a minimal member, then the small pair again.  Both small results equal, byte for byte, the one computed
+    before anything else here."""
+    import torch
+    small = [ref.planted(41, 30, 12)[:2]]
+    large = [ref.planted(42, 300, 30)[:2], ref.planted(43, 5, 2)[:2], ref.planted(44, 257, 40)[:2]]
+
+    def raw(pairs):
+        return b"".join(f.transformation.tobytes() + f.clique.tobytes() + np.array([f.status, f.clique_size, f.iterations, f.certified,
+                                                                                    f.nodes]).tobytes() for f in u.robust_fit_pairs(pairs, C_PLANTED))
+
+    first = raw(small)
+    with torch.cuda.stream(torch.cuda.Stream()):
+        runs = [raw(small), raw(large), raw(small)]
+    assert runs[0] == first and runs[2] == first and runs[1] == raw(large)
+    assert u.robust_fit_pairs(small, C_PLANTED)[0].status == 0

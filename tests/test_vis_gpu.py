@@ -299,3 +299,23 @@ def test_to_edge_closes_a_two_chain_pose_graph():
     # chain (10 steps of 0.5 m) by up to 5 e in each of two other axes, on top of the closure's own translation error e;
     # 1e-6 for the optimiser's stopping rule (abs_tol 1e-5 on a cost weighted by 1 / sigma^2)
     assert err <= reg_err * (1.0 + 2 * 5.0) + 1e-6
+
+
+def test_register_scratch_is_carved_afresh_for_every_batch():
+    """One stream, so one scratch block: a pair of 38 keypoints, then three larger pairs with an empty keyframe among them,
+    then the small pair again.  Both small results equal, bit for bit, the one computed before anything else here."""
+    import torch
+
+    def kf(seed, landmarks, distractors):
+        a, b = ref.keyframe_pair(seed, landmarks=landmarks, distractors=distractors)[:2]
+        return vr.Keyframe(*a), vr.Keyframe(*b)
+
+    none = vr.Keyframe(np.zeros((0, 2), np.float32), np.zeros((0, 3), np.float32), np.zeros((0, 32), np.uint8))
+    small, large = [kf(90, 30, 8)], [kf(91, 300, 100), (none, kf(92, 5, 0)[1]), kf(93, 257, 43)]
+    first = vr.register_pairs(small, CAM, min_inliers=8)[0]
+    with torch.cuda.stream(torch.cuda.Stream()):
+        runs = [vr.register_pairs(p, CAM, min_inliers=8) for p in (small, large, small)]
+    assert first.status == 0 and same(runs[0][0], first) and same(runs[2][0], first)
+    assert [g.status for g in runs[1]] == [0, 2, 0]
+    for g, w in zip(runs[1], vr.register_pairs(large, CAM, min_inliers=8)):
+        assert same(g, w)

@@ -226,3 +226,22 @@ def test_end_to_end_registration_from_raw_scans(vox, raw_street):
     # the scene and the seed of test_icp_cpu.test_staged_restatement_recovers_the_ground_truth (seed 100), and its bounds
     assert ref.rotation_error_deg(a.transformation[:3, :3], T_true[:3, :3]) <= 0.1
     assert np.linalg.norm(a.transformation[:3, 3] - T_true[:3, 3]) <= VOXEL / 5
+
+
+def test_scratch_is_carved_afresh_for_every_batch(vox):
+    """One stream, so one head block and one sort block: a cloud of 29 points (every piece but the histograms shorter than
+    256 bytes), then three larger clouds with an empty one among them, then the small cloud again.  Both small results equal,
+    byte for byte, the one computed before anything else here, and the reference."""
+    import torch
+    rng = np.random.default_rng(51)
+    small = [rng.uniform(-1.0, 1.0, (29, 3))]
+    large = [rng.uniform(-1.0, 1.0, (300, 3)), np.zeros((0, 3)), rng.uniform(-2.0, 2.0, (517, 3))]
+
+    def raw(clouds):
+        return b"".join(g.tobytes() + c.tobytes() for g, c in vox.downsample_clouds(clouds, VOXEL, counts=True))
+
+    first = raw(small)
+    with torch.cuda.stream(torch.cuda.Stream()):
+        runs = [raw(small), raw(large), raw(small)]
+    assert runs[0] == first and runs[2] == first and runs[1] == raw(large)
+    assert first.startswith(ref.voxel_average(small[0], VOXEL).tobytes())

@@ -142,6 +142,13 @@ _SIGNATURES = {
     "cslam_vis_register_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, C.c_double, _i, _i, _i, C.c_uint64,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_vis_hypotheses_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_feat_gray_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_feat_response_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_feat_select_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _i, C.c_double, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_feat_describe_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_feat_points_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_feat_extract_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, C.c_double, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _vp, _vp, _vp, _vp]),
     "cslam_wino4_fused_c64_h_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_h_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, _f, _vp, _vp, _vp]),
     "cslam_conv3x3_direct_r_dev": (_i, [_vp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp, C.c_float, _vp, _vp, _vp]),

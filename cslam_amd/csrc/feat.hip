@@ -1,0 +1,602 @@
+// feat.hip -- what a visual keyframe carries, from the image (gfx950): corners, steered BRIEF-32 descriptors, 3D points.
+//
+// Replaces RGBDHandler::compute_local_descriptors of src/front_end/rgbd_handler.cpp:266-312 (grey conversion, depth mask,
+// rtabmap's Feature2D::generateKeypoints / generateDescriptors / generateKeypoints3D) for a ragged batch of images.  rtabmap
+// and OpenCV are third party and were not available to compare against, and OpenCV's learned ORB / BRIEF sampling tables
+// are not ours to restate: parity with rtabmap's features is unpinned.  The algorithm is the one stated in
+// include/cslam_hip.h and feat.h; tests/feat_reference.py restates it in integer numpy, and the two agree bit for bit.
+//
+//   feat_gray_kernel     : a thread per pixel; 1 channel is copied, 3 (BGR) are weighted in integers.
+//   feat_response_kernel : a 16 x 16 tile of output pixels per workgroup.  The grey tile plus a 2-pixel halo in LDS, from it
+//                          Ix, Iy (int16) of the tile plus a 1-pixel halo, where a halo position outside the image holds the
+//                          derivative of its REFLECTED position (reflecting the grey image instead would flip the sign of
+//                          one derivative and with it of b).  Box sums in int32, the response in int64, the maximum of
+//                          an image by a wave reduction and one integer atomicMax per wave.
+//   feat_cand_kernel     : a thread per pixel: the candidate rule into a state map (0 none, 1 undecided candidate).
+//   feat_round_kernel    : a round of the greedy rule on the state map, a thread per pixel: an undecided candidate is
+//                          rejected when a higher-priority neighbour nearer than min_distance is accepted, accepted when all
+//                          of them are rejected (2 accepted, 3 rejected).  Both are final facts of the sequential rule, so
+//                          reading a state another wave has just written, or a stale one, changes no outcome, and the
+//                          highest-priority undecided candidate is decided in every round.  FEAT_WIDE_ROUNDS launches of it
+//                          use the whole chip; they leave few candidates undecided, and only long dependency chains.
+//   feat_select_kernel   : one workgroup of 512 per image.  (1) the candidates not yet rejected, in pixel order (prefix
+//                          counts over runs of 16 pixels per thread); (2) the remaining rounds, until none is undecided;
+//                          (3) the accepted ones in pixel order as
+//                          (Rmax - R) << 32 | pixel; (4) a stable LSD radix sort of the upper half, 4 bits per pass,
+//                          each thread a contiguous run, as many passes as the largest Rmax - R has digits: stable on a list
+//                          in pixel order is the index tie rule; (5) the first max_features.
+//                          The capacity of every list is H W: there is no overflow path.
+//   feat_describe_kernel : one wave per keypoint: the 37 x 37 grey patch in LDS, the moments over the disc of radius 15 by an
+//                          integer wave reduction, the bin, the separable binomial blur as unnormalised integer sums, the 256
+//                          tests 64 at a time with the bytes taken from __ballot.
+//   feat_points_kernel   : a thread per keypoint, float64.
+// A batch of n images occupies n workgroups in the selection, so a small batch leaves most of the chip idle there (accepted
+// as for the PnP kernel: DESIGN.md).
+#include "common.h"
+#include "feat.h"
+
+#define FEAT_TILE 16
+#define FEAT_SEL_BLOCK 512
+#define FEAT_SEL_WAVES (FEAT_SEL_BLOCK / 64)
+#define FEAT_SEL_RUN 16
+#define FEAT_WINDOW_RUN 16
+#define FEAT_MAX_DISTANCE 1024
+#define FEAT_WIDE_ROUNDS 4        // rounds of the greedy rule run over the whole chip before one workgroup per image finishes
+#define FEAT_MAX_PIXELS ((int64_t)1 << 30)
+
+typedef unsigned long long u64;
+
+__constant__ FeatPattern c_feat_pattern = feat_make_pattern();
+
+struct FeatImage { int64_t base; int H, W; };
+
+__device__ __forceinline__ FeatImage feat_image(const int64_t *off, const int32_t *hw, int c) {
+    FeatImage im = {off[c], hw[2 * c], hw[2 * c + 1]};
+    return im;
+}
+
+// ---- grey ----------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void feat_gray_kernel(const uint8_t *__restrict__ src, const int64_t *__restrict__ src_off,
+                                                        const int64_t *__restrict__ off, uint8_t *__restrict__ gray) {
+    const int c = blockIdx.y;
+    const int64_t n = off[c + 1] - off[c], i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const uint8_t *s = src + src_off[c];
+    if (src_off[c + 1] - src_off[c] == n) gray[off[c] + i] = s[i];
+    else gray[off[c] + i] = (uint8_t)feat_gray(s[3 * i], s[3 * i + 1], s[3 * i + 2]);
+}
+
+// ---- response ------------------------------------------------------------------------------------------------------
+__device__ __forceinline__ int feat_reflect(int i, int n) { return i < 0 ? -i : (i >= n ? 2 * n - 2 - i : i); }
+
+__global__ __launch_bounds__(FEAT_TILE * FEAT_TILE) void feat_response_kernel(const uint8_t *__restrict__ gray, const int64_t *__restrict__ off,
+                                                                              const int32_t *__restrict__ hw, int32_t *__restrict__ R,
+                                                                              int32_t *__restrict__ rmax) {
+    constexpr int G = FEAT_TILE + 4, D = FEAT_TILE + 2;
+    __shared__ uint8_t s_g[G * G];
+    __shared__ int16_t s_ix[D * D], s_iy[D * D];
+    const int c = blockIdx.z, t = threadIdx.x;
+    const FeatImage im = feat_image(off, hw, c);
+    const int H = im.H, W = im.W, y0 = blockIdx.y * FEAT_TILE, x0 = blockIdx.x * FEAT_TILE;
+    if (y0 >= H || x0 >= W) return;                        // the whole workgroup leaves
+    for (int e = t; e < G * G; e += FEAT_TILE * FEAT_TILE) {
+        const int yy = y0 - 2 + e / G, xx = x0 - 2 + e % G;
+        s_g[e] = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? gray[im.base + (int64_t)yy * W + xx] : (uint8_t)0;
+    }
+    __syncthreads();
+    for (int e = t; e < D * D; e += FEAT_TILE * FEAT_TILE) {
+        const int py = y0 - 1 + e / D, px = x0 - 1 + e % D;
+        if (py < -1 || py > H || px < -1 || px > W) continue;             // no output pixel of the image reads it
+        const int qy = feat_reflect(py, H), qx = feat_reflect(px, W);
+        // rows and columns qy - 1 .. qy + 1 reflected into the image all lie inside the grey tile (H, W >= 2)
+        const int r0 = feat_reflect(qy - 1, H) - (y0 - 2), r1 = qy - (y0 - 2), r2 = feat_reflect(qy + 1, H) - (y0 - 2);
+        const int c0 = feat_reflect(qx - 1, W) - (x0 - 2), c1 = qx - (x0 - 2), c2 = feat_reflect(qx + 1, W) - (x0 - 2);
+        const int g00 = s_g[r0 * G + c0], g01 = s_g[r0 * G + c1], g02 = s_g[r0 * G + c2];
+        const int g10 = s_g[r1 * G + c0], g12 = s_g[r1 * G + c2];
+        const int g20 = s_g[r2 * G + c0], g21 = s_g[r2 * G + c1], g22 = s_g[r2 * G + c2];
+        s_ix[e] = (int16_t)((g02 + 2 * g12 + g22) - (g00 + 2 * g10 + g20));
+        s_iy[e] = (int16_t)((g20 + 2 * g21 + g22) - (g00 + 2 * g01 + g02));
+    }
+    __syncthreads();
+    const int ty = t / FEAT_TILE, tx = t % FEAT_TILE, y = y0 + ty, x = x0 + tx;
+    int32_t r = 0;
+    if (y < H && x < W) {
+        int32_t a = 0, b = 0, cc = 0;
+#pragma unroll
+        for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+            for (int dx = 0; dx < 3; ++dx) {
+                const int ix = s_ix[(ty + dy) * D + tx + dx], iy = s_iy[(ty + dy) * D + tx + dx];
+                a += ix * ix; b += ix * iy; cc += iy * iy;
+            }
+        r = feat_response(a, b, cc);
+        R[im.base + (int64_t)y * W + x] = r;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { const int32_t v = __shfl_xor(r, o, 64); r = v > r ? v : r; }
+    if ((t & 63) == 0) atomicMax(&rmax[c], r);
+}
+
+// ---- candidates ----------------------------------------------------------------------------------------------------
+__device__ __forceinline__ bool feat_depth_valid(float d) { return d > 0.0f && d <= 3.4028234663852886e38f; }   // false for NaN, inf
+
+__global__ __launch_bounds__(256) void feat_cand_kernel(const int32_t *__restrict__ R, const int32_t *__restrict__ rmax,
+                                                        const uint8_t *__restrict__ valid, const float *__restrict__ depth,
+                                                        const int64_t *__restrict__ off, const int32_t *__restrict__ hw, double quality,
+                                                        int border, uint8_t *__restrict__ state) {
+    const int c = blockIdx.y;
+    const FeatImage im = feat_image(off, hw, c);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)im.H * im.W) return;
+    const int H = im.H, W = im.W, y = (int)(i / W), x = (int)(i % W);
+    const int32_t *Rc = R + im.base;
+    const int32_t r = Rc[i];
+    bool ok = y >= border && y <= H - 1 - border && x >= border && x <= W - 1 - border;
+    ok = ok && (double)r > quality * (double)rmax[c];
+    if (ok && valid) ok = valid[im.base + i] != 0;
+    if (ok && depth) ok = feat_depth_valid(depth[im.base + i]);
+    for (int dy = -1; dy <= 1 && ok; ++dy)
+        for (int dx = -1; dx <= 1; ++dx) {
+            const int yy = y + dy, xx = x + dx;
+            const int32_t v = (yy >= 0 && yy < H && xx >= 0 && xx < W) ? Rc[(int64_t)yy * W + xx] : -1;
+            ok = ok && r >= v;
+        }
+    state[im.base + i] = ok ? 1 : 0;
+}
+
+// ---- selection -----------------------------------------------------------------------------------------------------
+// exclusive prefix of v over the workgroup in thread order; *total = the sum.  s_w: FEAT_SEL_WAVES ints.
+__device__ __forceinline__ int feat_block_exscan(int v, int *s_w, int t, int *total) {
+    const int lane = t & 63, wave = t >> 6;
+    int inc = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) { const int y = __shfl_up(inc, o, 64); if (lane >= o) inc += y; }
+    __syncthreads();                                       // s_w of the previous call has been read
+    if (lane == 63) s_w[wave] = inc;
+    __syncthreads();
+    int before = 0, sum = 0;
+    for (int w = 0; w < FEAT_SEL_WAVES; ++w) { if (w < wave) before += s_w[w]; sum += s_w[w]; }
+    *total = sum;
+    return before + inc - v;
+}
+
+// The state map (0 none, 1 undecided, 2 accepted, 3 rejected) is read while other waves write it: relaxed atomics of the
+// scope the readers share.  A stale 1 only postpones a decision.
+template <int SCOPE> __device__ __forceinline__ int feat_state_load(const uint8_t *p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, SCOPE); }
+template <int SCOPE> __device__ __forceinline__ void feat_state_store(uint8_t *p, uint8_t v) { __hip_atomic_store(p, v, __ATOMIC_RELAXED, SCOPE); }
+
+// One step of the greedy rule for the undecided candidate `pix`: rejected when a candidate that comes before it (larger R,
+// then lower index) and lies nearer than md is accepted, accepted when all of those are rejected.  Both are final facts of
+// the sequential rule whenever they are read.  Returns true when it stays undecided.
+template <int SCOPE> __device__ __forceinline__ bool feat_decide(const int32_t *R, uint8_t *state, int H, int W, int md, int pix) {
+    const int y = pix / W, x = pix % W;
+    const int32_t r = R[pix];
+    bool blocked = false;
+    const int ya = y - (md - 1) < 0 ? 0 : y - (md - 1), yb = y + (md - 1) > H - 1 ? H - 1 : y + (md - 1);
+    const int xa = x - (md - 1) < 0 ? 0 : x - (md - 1), xb = x + (md - 1) > W - 1 ? W - 1 : x + (md - 1);
+    for (int yy = ya; yy <= yb; ++yy)
+        for (int x0 = xa; x0 <= xb; x0 += FEAT_WINDOW_RUN) {
+            int s[FEAT_WINDOW_RUN];                        // a run of states loaded side by side, then looked at: one latency
+#pragma unroll
+            for (int e = 0; e < FEAT_WINDOW_RUN; ++e) s[e] = x0 + e <= xb ? feat_state_load<SCOPE>(state + yy * W + x0 + e) : 0;
+#pragma unroll
+            for (int e = 0; e < FEAT_WINDOW_RUN; ++e) {
+                if (s[e] != 1 && s[e] != 2) continue;
+                const int dy = yy - y, dx = x0 + e - x, j = yy * W + x0 + e;
+                if (j == pix || dx * dx + dy * dy >= md * md) continue;
+                const int32_t rj = R[j];
+                if (!(rj > r || (rj == r && j < pix))) continue;              // j does not come before pix
+                if (s[e] == 2) { feat_state_store<SCOPE>(state + pix, 3); return false; }
+                blocked = true;
+            }
+        }
+    if (!blocked) feat_state_store<SCOPE>(state + pix, 2);
+    return blocked;
+}
+
+// a round over the whole image, a thread per pixel
+__global__ __launch_bounds__(256) void feat_round_kernel(const int32_t *__restrict__ R, const int64_t *__restrict__ off,
+                                                         const int32_t *__restrict__ hw, int md, uint8_t *state) {
+    const int c = blockIdx.y;
+    const FeatImage im = feat_image(off, hw, c);
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (int64_t)im.H * im.W) return;
+    if (feat_state_load<__HIP_MEMORY_SCOPE_AGENT>(state + im.base + i) != 1) return;
+    (void)feat_decide<__HIP_MEMORY_SCOPE_AGENT>(R + im.base, state + im.base, im.H, im.W, md, (int)i);
+}
+
+struct FeatSelArgs {
+    const int32_t *R; const int32_t *rmax; const int64_t *off; const int32_t *hw;
+    uint8_t *state; int32_t *cand; u64 *ka, *kb;           // scratch, [total pixels] each
+    int min_distance, max_features;
+    int32_t *count, *kp, *resp;                            // [n], [n, max_features, 2], [n, max_features]
+};
+
+__global__ __launch_bounds__(FEAT_SEL_BLOCK) void feat_select_kernel(FeatSelArgs A) {
+    __shared__ int s_w[FEAT_SEL_WAVES];
+    __shared__ int s_max;
+    __shared__ uint32_t s_h[16 * FEAT_SEL_BLOCK];
+    const int c = blockIdx.x, t = threadIdx.x;
+    const FeatImage im = feat_image(A.off, A.hw, c);
+    const int H = im.H, W = im.W, npix = H * W, md = A.min_distance;
+    const int32_t *R = A.R + im.base;
+    uint8_t *state = A.state + im.base;
+    int32_t *cand = A.cand + im.base;
+    const int32_t Rmax = A.rmax[c];
+
+    // (1) the candidates the rounds before have not rejected, in pixel order
+    int ncand = 0;
+    for (int p0 = 0; p0 < npix; p0 += FEAT_SEL_BLOCK * FEAT_SEL_RUN) {
+        const int p = p0 + t * FEAT_SEL_RUN;
+        int m = 0;
+        for (int e = 0; e < FEAT_SEL_RUN; ++e)
+            if (p + e < npix && (state[p + e] == 1 || state[p + e] == 2)) m |= 1 << e;
+        int tot;
+        int at = ncand + feat_block_exscan(__popc(m), s_w, t, &tot);
+        for (int e = 0; e < FEAT_SEL_RUN; ++e)
+            if (m >> e & 1) cand[at++] = p + e;
+        ncand += tot;
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    // (2) the remaining rounds of the greedy rule; every round decides a candidate, so ncand rounds are never exceeded
+    for (int round = 0; round <= ncand; ++round) {
+        int open = 0;
+        for (int k = t; k < ncand; k += FEAT_SEL_BLOCK) {
+            const int pix = cand[k];
+            if (feat_state_load<__HIP_MEMORY_SCOPE_WORKGROUP>(state + pix) != 1) continue;
+            if (feat_decide<__HIP_MEMORY_SCOPE_WORKGROUP>(R, state, H, W, md, pix)) open = 1;
+        }
+        __threadfence_block();
+        if (!__syncthreads_or(open)) break;
+    }
+
+    // (3) the accepted ones in pixel order
+    int n_acc = 0;
+    if (t == 0) s_max = 0;
+    for (int k0 = 0; k0 < ncand; k0 += FEAT_SEL_BLOCK) {
+        const int k = k0 + t;
+        int pix = -1;
+        if (k < ncand) { pix = cand[k]; if (feat_state_load<__HIP_MEMORY_SCOPE_WORKGROUP>(state + pix) != 2) pix = -1; }
+        int tot;
+        const int at = n_acc + feat_block_exscan(pix >= 0 ? 1 : 0, s_w, t, &tot);
+        if (pix >= 0) {
+            const int key = Rmax - R[pix];
+            A.ka[im.base + at] = ((u64)(uint32_t)key << 32) | (u64)(uint32_t)pix;
+            atomicMax(&s_max, key);
+        }
+        n_acc += tot;
+    }
+    __threadfence_block();
+    __syncthreads();
+
+    // (4) stable radix sort of the upper half
+    u64 *src = A.ka + im.base, *dst = A.kb + im.base;
+    const int per = (n_acc + FEAT_SEL_BLOCK - 1) / FEAT_SEL_BLOCK;
+    const int i0 = t * per < n_acc ? t * per : n_acc, i1 = i0 + per < n_acc ? i0 + per : n_acc;
+    const int key_max = s_max;
+    for (int shift = 32; shift < 64 && (key_max >> (shift - 32)) != 0; shift += 4) {
+        for (int d = 0; d < 16; ++d) s_h[d * FEAT_SEL_BLOCK + t] = 0;
+        for (int i = i0; i < i1; ++i) s_h[(int)((src[i] >> shift) & 15) * FEAT_SEL_BLOCK + t] += 1;
+        __syncthreads();
+        int sum = 0;
+        for (int e = 0; e < 16; ++e) sum += (int)s_h[16 * t + e];
+        int tot;
+        int at = feat_block_exscan(sum, s_w, t, &tot);
+        for (int e = 0; e < 16; ++e) { const int v = (int)s_h[16 * t + e]; s_h[16 * t + e] = (uint32_t)at; at += v; }
+        __syncthreads();
+        for (int i = i0; i < i1; ++i) {
+            const u64 key = src[i];
+            dst[s_h[(int)((key >> shift) & 15) * FEAT_SEL_BLOCK + t]++] = key;
+        }
+        __threadfence_block();
+        __syncthreads();
+        u64 *sw = src; src = dst; dst = sw;
+    }
+
+    // (5) the first max_features
+    const int n_out = n_acc < A.max_features ? n_acc : A.max_features;
+    for (int k = t; k < n_out; k += FEAT_SEL_BLOCK) {
+        const u64 key = src[k];
+        const int pix = (int)(uint32_t)key;
+        const int64_t o = (int64_t)c * A.max_features + k;
+        A.kp[2 * o] = pix % W;
+        A.kp[2 * o + 1] = pix / W;
+        A.resp[o] = Rmax - (int32_t)(key >> 32);
+    }
+    if (t == 0) A.count[c] = n_out;
+}
+
+// ---- keypoints of a batch: ragged (kp_off) or a fixed stride with counts --------------------------------------------
+struct FeatKeypoints { const int32_t *kp; const int64_t *kp_off; const int32_t *count; int stride; };
+
+__device__ __forceinline__ bool feat_keypoint_row(const FeatKeypoints &K, int c, int64_t k, int64_t *row) {
+    const int64_t n = K.kp_off ? K.kp_off[c + 1] - K.kp_off[c] : (int64_t)(K.count[c] < K.stride ? K.count[c] : K.stride);
+    *row = (K.kp_off ? K.kp_off[c] : (int64_t)c * K.stride) + k;
+    return k < n;
+}
+
+// ---- orientation and descriptors -----------------------------------------------------------------------------------
+__global__ __launch_bounds__(64) void feat_describe_kernel(const uint8_t *__restrict__ gray, const int64_t *__restrict__ off,
+                                                           const int32_t *__restrict__ hw, FeatKeypoints K, int32_t *__restrict__ bins,
+                                                           uint8_t *__restrict__ desc) {
+    constexpr int P = 2 * FEAT_MIN_BORDER + 1, B = 2 * FEAT_PATCH_RADIUS + 1, RAD = FEAT_PATCH_RADIUS;
+    __shared__ uint8_t s_p[P * P];
+    __shared__ uint16_t s_hb[P * B];
+    __shared__ int32_t s_b[B * B];
+    const int c = blockIdx.y, lane = threadIdx.x;
+    int64_t row;
+    if (!feat_keypoint_row(K, c, blockIdx.x, &row)) return;
+    const FeatImage im = feat_image(off, hw, c);
+    const int x = K.kp[2 * row], y = K.kp[2 * row + 1];
+    if (x < FEAT_MIN_BORDER || x > im.W - 1 - FEAT_MIN_BORDER || y < FEAT_MIN_BORDER || y > im.H - 1 - FEAT_MIN_BORDER) {
+        if (lane == 0) bins[row] = -1;                     // the patch would leave the image: nothing is read
+        if (lane < FEAT_DESC_BYTES) desc[FEAT_DESC_BYTES * row + lane] = 0;
+        return;
+    }
+    for (int e = lane; e < P * P; e += 64)
+        s_p[e] = gray[im.base + (int64_t)(y - FEAT_MIN_BORDER + e / P) * im.W + (x - FEAT_MIN_BORDER + e % P)];
+    __syncthreads();
+    int m10 = 0, m01 = 0;
+    for (int e = lane; e < B * B; e += 64) {
+        const int dy = e / B - RAD, dx = e % B - RAD;
+        if (dx * dx + dy * dy > RAD * RAD) continue;
+        const int I = s_p[(dy + FEAT_MIN_BORDER) * P + dx + FEAT_MIN_BORDER];
+        m10 += dx * I;
+        m01 += dy * I;
+    }
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { m10 += __shfl_xor(m10, o, 64); m01 += __shfl_xor(m01, o, 64); }
+    const int bin = feat_bin(m10, m01);
+    for (int e = lane; e < P * B; e += 64) {
+        const uint8_t *p = s_p + (e / B) * P + e % B;
+        s_hb[e] = (uint16_t)(p[0] + 6 * p[1] + 15 * p[2] + 20 * p[3] + 15 * p[4] + 6 * p[5] + p[6]);
+    }
+    __syncthreads();
+    for (int e = lane; e < B * B; e += 64) {
+        const uint16_t *p = s_hb + e;
+        s_b[e] = p[0] + 6 * p[B] + 15 * p[2 * B] + 20 * p[3 * B] + 15 * p[4 * B] + 6 * p[5 * B] + p[6 * B];
+    }
+    __syncthreads();
+    for (int r = 0; r < FEAT_PAIRS / 64; ++r) {
+        const int8_t *pq = c_feat_pattern.v[r * 64 + lane];
+        int px, py, qx, qy;
+        feat_rotate(pq[0], pq[1], bin, &px, &py);
+        feat_rotate(pq[2], pq[3], bin, &qx, &qy);
+        const u64 m = __ballot(s_b[(py + RAD) * B + px + RAD] < s_b[(qy + RAD) * B + qx + RAD]);
+        if (lane < 8) desc[FEAT_DESC_BYTES * row + 8 * r + lane] = (uint8_t)(m >> (8 * lane));
+    }
+    if (lane == 0) bins[row] = bin;
+}
+
+// ---- 3D points -----------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void feat_points_kernel(const float *__restrict__ depth, const int64_t *__restrict__ off,
+                                                          const int32_t *__restrict__ hw, FeatKeypoints K, const double *__restrict__ cams,
+                                                          double *__restrict__ pts) {
+    const int c = blockIdx.y;
+    int64_t row;
+    if (!feat_keypoint_row(K, c, (int64_t)blockIdx.x * 256 + threadIdx.x, &row)) return;
+    const FeatImage im = feat_image(off, hw, c);
+    const int u = K.kp[2 * row], v = K.kp[2 * row + 1];
+    const double fx = cams[4 * c], fy = cams[4 * c + 1], cx = cams[4 * c + 2], cy = cams[4 * c + 3];
+    double X = NAN, Y = NAN, Z = NAN;
+    if (u >= 0 && u < im.W && v >= 0 && v < im.H) {
+        const float d = depth[im.base + (int64_t)v * im.W + u];
+        if (feat_depth_valid(d)) {
+            Z = (double)d;
+            X = (((double)u - cx) * Z) / fx;
+            Y = (((double)v - cy) * Z) / fy;
+        }
+    }
+    pts[3 * row] = X; pts[3 * row + 1] = Y; pts[3 * row + 2] = Z;
+}
+
+// ---- host side -----------------------------------------------------------------------------------------------------
+static StreamScratch g_feat_scratch;
+
+struct FeatShape { RaggedShape px; int max_h, max_w; };
+
+// the host copies are required: they size the launches.  Every image is H x W = its rows of the offsets.
+static int feat_shape(const int64_t *h_off, const int32_t *h_hw, int n, FeatShape *s) {
+    BATCH_COUNT_CHECK(n);
+    ARG_CHECK(h_off != nullptr && h_hw != nullptr, "h_off and h_hw are required");
+    int rc = offsets_check(h_off, n, &s->px);
+    if (rc) return rc;
+    s->max_h = s->max_w = 0;
+    for (int c = 0; c < n; ++c) {
+        const int64_t H = h_hw[2 * c], W = h_hw[2 * c + 1];
+        ARG_CHECK(H >= 2 && W >= 2, "an image is at least 2 x 2");
+        ARG_CHECK(H * W == h_off[c + 1] - h_off[c], "the offsets must hold H * W pixels per image");
+        if (H > s->max_h) s->max_h = (int)H;
+        if (W > s->max_w) s->max_w = (int)W;
+    }
+    ARG_CHECK(s->px.largest <= FEAT_MAX_PIXELS, "an image has at most 2^30 pixels");
+    ARG_CHECK(ceil_div64(s->max_h, FEAT_TILE) <= 65535, "an image has at most 65535 * 16 rows");
+    return CSLAM_OK;
+}
+
+static int feat_src_check(const int64_t *h_src_off, const int64_t *h_off, int n) {
+    ARG_CHECK(h_src_off != nullptr, "h_src_off is required");
+    RaggedShape s;
+    int rc = offsets_check(h_src_off, n, &s);
+    if (rc) return rc;
+    for (int c = 0; c < n; ++c) {
+        const int64_t bytes = h_src_off[c + 1] - h_src_off[c], px = h_off[c + 1] - h_off[c];
+        ARG_CHECK(bytes == px || bytes == 3 * px, "an image has 1 channel or 3 (BGR)");
+    }
+    return CSLAM_OK;
+}
+
+static int feat_select_checks(double quality, int min_distance, int border, int max_features) {
+    ARG_CHECK(quality >= 0.0 && quality <= 1.0, "quality_level must be in [0, 1]");
+    ARG_CHECK(min_distance >= 1 && min_distance <= FEAT_MAX_DISTANCE, "min_distance must be in [1, 1024]");
+    ARG_CHECK(border >= FEAT_MIN_BORDER, "border must be at least 18 (patch radius 15 plus blur radius 3)");
+    ARG_CHECK(max_features >= 1 && max_features <= 65535, "max_features must be in [1, 65535]");
+    return CSLAM_OK;
+}
+
+static int feat_kp_shape(const int64_t *h_kp_off, int n, RaggedShape *s) {
+    ARG_CHECK(h_kp_off != nullptr, "h_kp_off is required");
+    int rc = offsets_check(h_kp_off, n, s);
+    if (rc) return rc;
+    ARG_CHECK(s->largest <= 0x7fffffffll, "too many keypoints in one image");
+    return CSLAM_OK;
+}
+
+struct FeatSelScratch { uint8_t *state; int32_t *cand; u64 *ka, *kb; };
+static void feat_sel_carve(Carver &cv, size_t total, FeatSelScratch *s) {
+    s->state = cv.take<uint8_t>(total);
+    s->cand = cv.take<int32_t>(total);
+    s->ka = cv.take<u64>(total);
+    s->kb = cv.take<u64>(total);
+}
+
+static void feat_launch_gray(const uint8_t *src, const int64_t *src_off, const int64_t *off, int n, const FeatShape &sh, uint8_t *gray,
+                             hipStream_t st) {
+    hipLaunchKernelGGL(feat_gray_kernel, dim3((unsigned)ceil_div64(sh.px.largest, 256), (unsigned)n), dim3(256), 0, st, src, src_off, off, gray);
+}
+
+static int feat_launch_response(const uint8_t *gray, const int64_t *off, const int32_t *hw, int n, const FeatShape &sh, int32_t *R,
+                                int32_t *rmax, hipStream_t st) {
+    HIP_TRY(hipMemsetAsync(rmax, 0, sizeof(int32_t) * (size_t)n, st));
+    hipLaunchKernelGGL(feat_response_kernel, dim3((unsigned)ceil_div64(sh.max_w, FEAT_TILE), (unsigned)ceil_div64(sh.max_h, FEAT_TILE), (unsigned)n),
+                       dim3(FEAT_TILE * FEAT_TILE), 0, st, gray, off, hw, R, rmax);
+    return CSLAM_OK;
+}
+
+static void feat_launch_select(const int32_t *R, const int32_t *rmax, const uint8_t *valid, const float *depth, const int64_t *off,
+                               const int32_t *hw, int n, const FeatShape &sh, double quality, int min_distance, int border, int max_features,
+                               const FeatSelScratch &s, int32_t *count, int32_t *kp, int32_t *resp, hipStream_t st) {
+    hipLaunchKernelGGL(feat_cand_kernel, dim3((unsigned)ceil_div64(sh.px.largest, 256), (unsigned)n), dim3(256), 0, st, R, rmax, valid, depth, off,
+                       hw, quality, border, s.state);
+    for (int round = 0; round < FEAT_WIDE_ROUNDS; ++round)
+        hipLaunchKernelGGL(feat_round_kernel, dim3((unsigned)ceil_div64(sh.px.largest, 256), (unsigned)n), dim3(256), 0, st, R, off, hw, min_distance,
+                           s.state);
+    FeatSelArgs a = {R, rmax, off, hw, s.state, s.cand, s.ka, s.kb, min_distance, max_features, count, kp, resp};
+    hipLaunchKernelGGL(feat_select_kernel, dim3((unsigned)n), dim3(FEAT_SEL_BLOCK), 0, st, a);
+}
+
+static void feat_launch_describe(const uint8_t *gray, const int64_t *off, const int32_t *hw, int n, const FeatKeypoints &K, int64_t most,
+                                 int32_t *bins, uint8_t *desc, hipStream_t st) {
+    if (most > 0)
+        hipLaunchKernelGGL(feat_describe_kernel, dim3((unsigned)most, (unsigned)n), dim3(64), 0, st, gray, off, hw, K, bins, desc);
+}
+
+static void feat_launch_points(const float *depth, const int64_t *off, const int32_t *hw, int n, const FeatKeypoints &K, int64_t most,
+                               const double *cams, double *pts, hipStream_t st) {
+    if (most > 0)
+        hipLaunchKernelGGL(feat_points_kernel, dim3((unsigned)ceil_div64(most, 256), (unsigned)n), dim3(256), 0, st, depth, off, hw, K, cams, pts);
+}
+
+CSLAM_API int cslam_feat_gray_dev(const uint8_t *d_src, const int64_t *d_src_off, const int64_t *d_off, const int32_t *d_hw, int n,
+                                  uint8_t *d_gray, const int64_t *h_src_off, const int64_t *h_off, const int32_t *h_hw, void *stream) {
+    FeatShape sh;
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_src_check(h_src_off, h_off, n))) return rc;
+    ARG_CHECK(d_src && d_src_off && d_off && d_hw && d_gray, "NULL argument");
+    PTR_DEVICE(d_src);
+    feat_launch_gray(d_src, d_src_off, d_off, n, sh, d_gray, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_response_dev(const uint8_t *d_gray, const int64_t *d_off, const int32_t *d_hw, int n, int32_t *d_R,
+                                      int32_t *d_rmax, const int64_t *h_off, const int32_t *h_hw, void *stream) {
+    FeatShape sh;
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    ARG_CHECK(d_gray && d_off && d_hw && d_R && d_rmax, "NULL argument");
+    PTR_DEVICE(d_gray);
+    if ((rc = feat_launch_response(d_gray, d_off, d_hw, n, sh, d_R, d_rmax, (hipStream_t)stream))) return rc;
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_select_dev(const int32_t *d_R, const int32_t *d_rmax, const uint8_t *d_valid, const int64_t *d_off,
+                                    const int32_t *d_hw, int n, double quality_level, int min_distance, int border, int max_features,
+                                    int32_t *d_count, int32_t *d_kp, int32_t *d_resp, const int64_t *h_off, const int32_t *h_hw,
+                                    void *stream) {
+    FeatShape sh;
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_select_checks(quality_level, min_distance, border, max_features))) return rc;
+    ARG_CHECK(d_R && d_rmax && d_off && d_hw && d_count && d_kp && d_resp, "NULL argument");
+    PTR_DEVICE(d_R);
+    hipStream_t st = (hipStream_t)stream;
+    FeatSelScratch s;
+    auto layout = [&](Carver &cv) { feat_sel_carve(cv, (size_t)sh.px.total, &s); };
+    SCRATCH_CARVE(g_feat_scratch, st, (size_t)1 << 20, layout);
+    feat_launch_select(d_R, d_rmax, d_valid, nullptr, d_off, d_hw, n, sh, quality_level, min_distance, border, max_features, s, d_count, d_kp,
+                       d_resp, st);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_describe_dev(const uint8_t *d_gray, const int64_t *d_off, const int32_t *d_hw, int n, const int32_t *d_kp,
+                                      const int64_t *d_kp_off, int32_t *d_bins, uint8_t *d_desc, const int64_t *h_off,
+                                      const int32_t *h_hw, const int64_t *h_kp_off, void *stream) {
+    FeatShape sh;
+    RaggedShape ks;
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_kp_shape(h_kp_off, n, &ks))) return rc;
+    ARG_CHECK(d_gray && d_off && d_hw && d_kp && d_kp_off && d_bins && d_desc, "NULL argument");
+    PTR_DEVICE(d_gray);
+    FeatKeypoints K = {d_kp, d_kp_off, nullptr, 0};
+    feat_launch_describe(d_gray, d_off, d_hw, n, K, ks.largest, d_bins, d_desc, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_points_dev(const float *d_depth, const int64_t *d_off, const int32_t *d_hw, int n, const int32_t *d_kp,
+                                    const int64_t *d_kp_off, const double *d_cameras, double *d_points, const int64_t *h_off,
+                                    const int32_t *h_hw, const int64_t *h_kp_off, void *stream) {
+    FeatShape sh;
+    RaggedShape ks;
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_kp_shape(h_kp_off, n, &ks))) return rc;
+    ARG_CHECK(d_depth && d_off && d_hw && d_kp && d_kp_off && d_cameras && d_points, "NULL argument");
+    PTR_DEVICE(d_depth);
+    FeatKeypoints K = {d_kp, d_kp_off, nullptr, 0};
+    feat_launch_points(d_depth, d_off, d_hw, n, K, ks.largest, d_cameras, d_points, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_extract_dev(const uint8_t *d_src, const int64_t *d_src_off, const float *d_depth, const int64_t *d_off,
+                                     const int32_t *d_hw, const double *d_cameras, int n, double quality_level, int min_distance,
+                                     int border, int max_features, int depth_as_mask, int32_t *d_count, int32_t *d_kp, int32_t *d_resp,
+                                     int32_t *d_bins, uint8_t *d_desc, double *d_points, const int64_t *h_src_off, const int64_t *h_off,
+                                     const int32_t *h_hw, void *stream) {
+    FeatShape sh;
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_src_check(h_src_off, h_off, n))) return rc;
+    if ((rc = feat_select_checks(quality_level, min_distance, border, max_features))) return rc;
+    ARG_CHECK(d_src && d_src_off && d_depth && d_off && d_hw && d_cameras && d_count && d_kp && d_resp && d_bins && d_desc && d_points,
+              "NULL argument");
+    PTR_DEVICE(d_src);
+    hipStream_t st = (hipStream_t)stream;
+    FeatSelScratch s;
+    uint8_t *gray;
+    int32_t *R, *rmax;
+    auto layout = [&](Carver &cv) {
+        gray = cv.take<uint8_t>((size_t)sh.px.total);
+        R = cv.take<int32_t>((size_t)sh.px.total);
+        rmax = cv.take<int32_t>((size_t)n);
+        feat_sel_carve(cv, (size_t)sh.px.total, &s);
+    };
+    SCRATCH_CARVE(g_feat_scratch, st, (size_t)1 << 20, layout);
+    feat_launch_gray(d_src, d_src_off, d_off, n, sh, gray, st);
+    if ((rc = feat_launch_response(gray, d_off, d_hw, n, sh, R, rmax, st))) return rc;
+    feat_launch_select(R, rmax, nullptr, depth_as_mask ? d_depth : nullptr, d_off, d_hw, n, sh, quality_level, min_distance, border,
+                       max_features, s, d_count, d_kp, d_resp, st);
+    FeatKeypoints K = {d_kp, nullptr, d_count, max_features};
+    feat_launch_describe(gray, d_off, d_hw, n, K, max_features, d_bins, d_desc, st);
+    feat_launch_points(d_depth, d_off, d_hw, n, K, max_features, d_cameras, d_points, st);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}

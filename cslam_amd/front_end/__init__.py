@@ -1,1 +1,5 @@
-"""The front end's geometric verification of loop closures (visual_registration.py)."""
+"""The front end on the GPU: what a visual keyframe carries, from the image (visual_features.py), and the geometric
+verification of loop closures between such keyframes (visual_registration.py)."""
+from .visual_features import (back_project, corner_response, describe, extract_features, extract_keyframes, is_new_keyframe,  # noqa: F401
+                              select_keypoints, to_gray)
+from .visual_registration import Keyframe, compute_transformation, register_pairs  # noqa: F401

@@ -696,6 +696,83 @@ int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d_points_fr
                            int refine_iterations, int refine_rounds, uint64_t seed, int32_t *d_rows, int32_t *d_count, double *d_T,
                            int32_t *d_info, int32_t *d_flags, const int64_t *h_from_off, const int64_t *h_to_off, void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Visual keyframes: corners, steered BRIEF-32 descriptors and 3D points from the image (csrc/feat.hip, csrc/feat.h).
+ * Replaces RGBDHandler::compute_local_descriptors of src/front_end/rgbd_handler.cpp:266-312 (grey conversion, depth mask,
+ * rtabmap's Feature2D::generateKeypoints, generateDescriptors, generateKeypoints3D), whose result feeds the keyframe
+ * decision of generate_new_keyframe (:314-351) and every later computeTransformation.  rtabmap and OpenCV are third party
+ * and were not available, and OpenCV's learned ORB / BRIEF sampling tables are not ours to restate: parity with rtabmap's
+ * features is unpinned and stays so.  What is pinned is the algorithm stated here, which is integer arithmetic from the
+ * image to the descriptors: the GPU, csrc/feat.h on the host and tests/feat_reference.py agree bit for bit.  Matching only
+ * needs every robot to use the same rule.
+ *
+ * A batch is ragged: n images of their own sizes, d_off int64 [n + 1] PIXEL offsets, d_hw int32 [n, 2] = (H, W) with
+ * H W = the image's pixels, H, W >= 2.  h_off / h_hw: the same on the host (required; they size the launches).  The result
+ * for an image is the same bytes alone or in any batch.  x runs to the right, y downwards; a keypoint is (x, y) int32.
+ *
+ * Grey: one channel is taken as it is; three are B, G, R: gray = (1868 B + 9617 G + 4899 R + 8192) >> 14.
+ * Response (Shi-Tomasi, exact): Ix, Iy = 3 x 3 Sobel on the uint8 image, the border reflected without repeating the edge
+ *   pixel (index -1 -> 1, n -> n - 2), |.| <= 1020; a = sum Ix^2, b = sum Ix Iy, c = sum Iy^2 over the 3 x 3 box with the
+ *   same border rule applied to the derivative maps; T = a + c, D = (a - c)^2 + 4 b^2 in int64 (<= 4.4e14),
+ *   R = T - isqrt(D) with the exact integer floor square root: twice the smaller eigenvalue of the structure matrix,
+ *   floored to a unit, in [0, 1.9e7], int32.  Rmax = the maximum over the image.
+ * Candidates: a pixel with (double)R > quality_level * (double)Rmax (one multiplication), R >= each of its 8 neighbours
+ *   (outside the image: -1), at least `border` pixels from every edge (border <= x <= W - 1 - border; border >= 18 = patch
+ *   radius 15 + blur radius 3) and, with a mask or a depth image, valid there.  Their order: R descending, then the pixel
+ *   index y W + x ascending (the key (Rmax - R) << 32 | y W + x ascending).
+ * Selection = the sequential greedy rule: walk the candidates in that order, accept one iff no candidate accepted earlier
+ *   lies nearer than min_distance (dx^2 + dy^2 < min_distance^2 on integers), stop after max_features.
+ * Orientation: m10 = sum x I, m01 = sum y I over the disc x^2 + y^2 <= 15^2 around the keypoint on the grey image;
+ *   bin = argmax_k (m10 C_k + m01 S_k) in int64, the lowest k on ties; (C_k, S_k), k = 0 .. 7 = (16384, 0), (16069, 3196),
+ *   (15137, 6270), (13623, 9102), (11585, 11585), (9102, 13623), (6270, 15137), (3196, 16069); bins 8 .. 31 by exact
+ *   quarter turns (c, s) -> (-s, c).
+ * Descriptor (steered BRIEF-32): the grey patch blurred by the separable binomial kernel [1, 6, 15, 20, 15, 6, 1] in both
+ *   directions, kept as unnormalised integer sums.  The base pattern = 256 point pairs (p, q) from the stateless generator
+ *   of feat.h: draw n = splitmix64(0x0BADC0FFEE0DDF00 + n), x = (low 32 bits) mod 27 - 13, y = (high 32 bits) mod 27 - 13,
+ *   kept when x^2 + y^2 <= 13^2; a pair = the next two kept points, drawn again when q = p.  The pattern of bin k: each
+ *   point rotated by (C, S) of k mod 8, ((x C - y S), (x S + y C)) / 16384 rounded half away from zero in integers, then
+ *   k / 8 quarter turns (x, y) -> (-y, x).  Bit i = blur(p_i) < blur(q_i), bit i mod 8 of byte i / 8.
+ * Points (generateKeypoints3D): depth float32 metres of the image's size, valid iff finite and > 0; in float64
+ *   X = ((u - cx) d) / fx, Y = ((v - cy) d) / fy, Z = d; a keypoint without valid depth gives a NaN row.
+ * Out of scope: the stereo handler, depth images smaller than the colour image, scale pyramids, sub-pixel refinement. */
+/* cslam_feat_gray_dev -- the grey conversion of rgbd_handler.cpp:266-312.  d_src uint8, image c = the bytes
+ *   [d_src_off[c], d_src_off[c + 1]): H W of them (one channel) or 3 H W (B, G, R interleaved).  d_gray uint8 [total pixels]. */
+int cslam_feat_gray_dev(const uint8_t *d_src, const int64_t *d_src_off, const int64_t *d_off, const int32_t *d_hw, int n,
+                        uint8_t *d_gray, const int64_t *h_src_off, const int64_t *h_off, const int32_t *h_hw, void *stream);
+/* cslam_feat_response_dev -- the corner measure inside generateKeypoints (rgbd_handler.cpp:266-312): grey images ->
+ *   d_R int32 [total pixels], d_rmax int32 [n]. */
+int cslam_feat_response_dev(const uint8_t *d_gray, const int64_t *d_off, const int32_t *d_hw, int n, int32_t *d_R, int32_t *d_rmax,
+                            const int64_t *h_off, const int32_t *h_hw, void *stream);
+/* cslam_feat_select_dev -- the keypoints of generateKeypoints (rgbd_handler.cpp:266-312) from a response map, which is an
+ *   input so that a map can be constructed: d_R, d_rmax as above, d_valid NULL or uint8 [total pixels] (0: masked out, the
+ *   depth mask of the reference).  quality_level in [0, 1], min_distance in [1, 1024], border >= 18, max_features in
+ *   [1, 65535].  d_count int32 [n]; d_kp int32 [n, max_features, 2] = (x, y) and d_resp int32 [n, max_features], the first
+ *   d_count[c] rows of image c written. */
+int cslam_feat_select_dev(const int32_t *d_R, const int32_t *d_rmax, const uint8_t *d_valid, const int64_t *d_off, const int32_t *d_hw,
+                          int n, double quality_level, int min_distance, int border, int max_features, int32_t *d_count, int32_t *d_kp,
+                          int32_t *d_resp, const int64_t *h_off, const int32_t *h_hw, void *stream);
+/* cslam_feat_describe_dev -- generateDescriptors (rgbd_handler.cpp:266-312): grey images and ragged keypoints d_kp int32
+ *   [total, 2] with d_kp_off int64 [n + 1] (h_kp_off: the same on the host, required) -> d_bins int32 [total], d_desc uint8
+ *   [total, 32].  A keypoint nearer than 18 pixels to an edge reads nothing: bin -1, descriptor 0. */
+int cslam_feat_describe_dev(const uint8_t *d_gray, const int64_t *d_off, const int32_t *d_hw, int n, const int32_t *d_kp,
+                            const int64_t *d_kp_off, int32_t *d_bins, uint8_t *d_desc, const int64_t *h_off, const int32_t *h_hw,
+                            const int64_t *h_kp_off, void *stream);
+/* cslam_feat_points_dev -- generateKeypoints3D (rgbd_handler.cpp:266-312): d_depth float32 [total pixels], keypoints as
+ *   above, d_cameras float64 [n, 4] = (fx, fy, cx, cy) -> d_points float64 [total, 3].  A keypoint outside its image gives
+ *   a NaN row. */
+int cslam_feat_points_dev(const float *d_depth, const int64_t *d_off, const int32_t *d_hw, int n, const int32_t *d_kp,
+                          const int64_t *d_kp_off, const double *d_cameras, double *d_points, const int64_t *h_off, const int32_t *h_hw,
+                          const int64_t *h_kp_off, void *stream);
+/* cslam_feat_extract_dev -- the whole of compute_local_descriptors (rgbd_handler.cpp:266-312) on one stream with no host
+ *   wait in between: grey, response, selection (depth_as_mask != 0: only pixels of valid depth are candidates), bins and
+ *   descriptors, points.  Outputs in the layout of cslam_feat_select_dev: d_count [n], d_kp [n, max_features, 2], d_resp and
+ *   d_bins [n, max_features], d_desc [n, max_features, 32], d_points [n, max_features, 3]. */
+int cslam_feat_extract_dev(const uint8_t *d_src, const int64_t *d_src_off, const float *d_depth, const int64_t *d_off,
+                           const int32_t *d_hw, const double *d_cameras, int n, double quality_level, int min_distance, int border,
+                           int max_features, int depth_as_mask, int32_t *d_count, int32_t *d_kp, int32_t *d_resp, int32_t *d_bins,
+                           uint8_t *d_desc, double *d_points, const int64_t *h_src_off, const int64_t *h_off, const int32_t *h_hw,
+                           void *stream);
+
 /* Winograd F(2x2, 3x3) transforms for the 3x3 / stride 1 / pad 1 convolutions of the extractor backbone
  * (the VGG-16 trunk built at cslam/vpr/netvlad.py:163-171; the reference runs it through torch's direct
  * convolution).  Activations are NHWC float32.  conv(x, g) + bias = output(bmm(input(x), U)) with

@@ -1,0 +1,120 @@
+"""Times of the keyframe features (csrc/feat.hip) by HIP events: one 480 x 640 BGR frame and a batch of 16, each stage
+apart (grey, response, selection, bins and descriptors, points) and the whole chain.  Prints one JSON line.
+
+    python tools/perf_visual_features.py [--reps 20]
+"""
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+
+sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."))
+
+
+def frame(seed, H, W):
+    """Random grey blocks of 6 .. 12 pixels, smoothed once, in three channels: some thousand corner candidates."""
+    rng = np.random.default_rng(seed)
+    b = 6 + seed % 7
+    cells = rng.integers(0, 256, size=((H + b - 1) // b, (W + b - 1) // b)).astype(np.float32)
+    g = np.kron(cells, np.ones((b, b), dtype=np.float32))[:H, :W]
+    g = (g + np.roll(g, 1, axis=0) + np.roll(g, 1, axis=1) + np.roll(g, (1, 1), axis=(0, 1))) / 4 + rng.normal(0.0, 2.0, (H, W))
+    g = np.clip(np.round(g), 0, 255).astype(np.uint8)
+    return np.ascontiguousarray(np.stack([g, np.roll(g, 1, axis=1), np.roll(g, 1, axis=0)], axis=2))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--height", type=int, default=480)
+    ap.add_argument("--width", type=int, default=640)
+    ap.add_argument("--max-features", type=int, default=1000)
+    args = ap.parse_args()
+    import torch
+    from cslam_amd import _lib
+    from cslam_amd.lidar_pr._batch import host, offsets, stream, to_dev
+    _lib.require_gpu()
+    lib = _lib.load()
+    dev = torch.device("cuda", 0)
+    H, W, mf = args.height, args.width, args.max_features
+    out = {"height": H, "width": W, "max_features": mf, "reps": args.reps, "device": torch.cuda.get_device_name(0)}
+    for batch in (1, 16):
+        imgs = [frame(s, H, W) for s in range(min(batch, 4))]
+        imgs = [imgs[k % len(imgs)] for k in range(batch)]
+        rng = np.random.default_rng(0)
+        depth = (1.0 + 4.0 * rng.random((batch, H, W))).astype(np.float32)
+        depth[:, :, W // 3:W // 3 + 20] = 0.0
+        off, src_off = offsets([H * W] * batch), offsets([3 * H * W] * batch)
+        hw = np.tile(np.array([[H, W]], dtype=np.int32), (batch, 1))
+        t_src, t_depth = to_dev(np.concatenate([i.reshape(-1) for i in imgs]), dev), to_dev(depth.reshape(-1), dev)
+        t_off, t_so, t_hw = to_dev(off, dev), to_dev(src_off, dev), to_dev(hw, dev)
+        t_cam = to_dev(np.tile(np.array([525.0, 525.0, W / 2 - 0.5, H / 2 - 0.5]), (batch, 1)), dev)
+        total = batch * H * W
+        t_gray = torch.zeros(total, dtype=torch.uint8, device=dev)
+        t_R = torch.zeros(total, dtype=torch.int32, device=dev)
+        t_max = torch.zeros(batch, dtype=torch.int32, device=dev)
+        t_valid = (t_depth > 0).to(torch.uint8)
+        t_cnt = torch.zeros(batch, dtype=torch.int32, device=dev)
+        t_kp = torch.zeros((batch, mf, 2), dtype=torch.int32, device=dev)
+        t_resp = torch.zeros((batch, mf), dtype=torch.int32, device=dev)
+        t_bins = torch.zeros((batch, mf), dtype=torch.int32, device=dev)
+        t_desc = torch.zeros((batch, mf, 32), dtype=torch.uint8, device=dev)
+        t_pts = torch.zeros((batch, mf, 3), dtype=torch.float64, device=dev)
+        k_off = offsets([mf] * batch)                      # the staged entries take the rows as ragged: here all mf per image
+        t_ko = to_dev(k_off, dev)
+        h = (host(off), host(hw))
+
+        def gray():
+            _lib.check(lib.cslam_feat_gray_dev(t_src.data_ptr(), t_so.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch, t_gray.data_ptr(),
+                                               host(src_off), *h, stream()))
+
+        def response():
+            _lib.check(lib.cslam_feat_response_dev(t_gray.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch, t_R.data_ptr(), t_max.data_ptr(),
+                                                   *h, stream()))
+
+        def select():
+            _lib.check(lib.cslam_feat_select_dev(t_R.data_ptr(), t_max.data_ptr(), t_valid.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch,
+                                                 0.001, 7, 19, mf, t_cnt.data_ptr(), t_kp.data_ptr(), t_resp.data_ptr(), *h, stream()))
+
+        def describe():
+            _lib.check(lib.cslam_feat_describe_dev(t_gray.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch, t_kp.data_ptr(), t_ko.data_ptr(),
+                                                   t_bins.data_ptr(), t_desc.data_ptr(), *h, host(k_off), stream()))
+
+        def points():
+            _lib.check(lib.cslam_feat_points_dev(t_depth.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch, t_kp.data_ptr(), t_ko.data_ptr(),
+                                                 t_cam.data_ptr(), t_pts.data_ptr(), *h, host(k_off), stream()))
+
+        def chain():
+            _lib.check(lib.cslam_feat_extract_dev(t_src.data_ptr(), t_so.data_ptr(), t_depth.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(),
+                                                  t_cam.data_ptr(), batch, 0.001, 7, 19, mf, 1, t_cnt.data_ptr(), t_kp.data_ptr(),
+                                                  t_resp.data_ptr(), t_bins.data_ptr(), t_desc.data_ptr(), t_pts.data_ptr(), host(src_off), *h,
+                                                  stream()))
+
+        def timed(fn):
+            for _ in range(3):
+                fn()
+            torch.cuda.synchronize()
+            ms = []
+            for _ in range(args.reps):
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                fn()
+                e1.record()
+                e1.synchronize()
+                ms.append(e0.elapsed_time(e1))
+            return round(float(np.median(ms)), 4)
+
+        res = {"gray_ms": timed(gray), "response_ms": timed(response), "select_ms": timed(select)}
+        cnt = t_cnt.cpu().numpy()
+        if not np.all(cnt == mf):                          # the staged describe / points read all mf rows of an image
+            t_kp[:, :, 0].clamp_(18, W - 19)
+            t_kp[:, :, 1].clamp_(18, H - 19)
+        res.update({"describe_ms": timed(describe), "points_ms": timed(points), "chain_ms": timed(chain)})
+        res["keypoints_per_image"] = round(float(t_cnt.cpu().numpy().mean()), 1)
+        out["batch_%d" % batch] = res
+    print(json.dumps(out))
+
+
+if __name__ == "__main__":
+    main()

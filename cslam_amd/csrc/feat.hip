@@ -30,10 +30,17 @@
 //                          integer wave reduction, the bin, the separable binomial blur as unnormalised integer sums, the 256
 //                          tests 64 at a time with the bytes taken from __ballot.
 //   feat_points_kernel   : a thread per keypoint, float64.
+//   feat_stereo_kernel   : the stereo frame's depth (stereo_handler.cpp:148-227 in place of the depth image at rgbd_handler.cpp:309):
+//                          one wave per keypoint.  The 3 x 15 left window and the right strip of the whole disparity range in
+//                          LDS, a disparity per lane and round (at most 5), the costs kept in LDS, the best by a wave minimum
+//                          of (cost << 9 | d), the second best by another with the neighbours of the best masked out; for
+//                          the left-right check the right window and the mirrored left strip take the same buffers.  The
+//                          rules are stereo.h's.  No atomics; a keypoint's result depends on nothing else in the batch.
 // A batch of n images occupies n workgroups in the selection, so a small batch leaves most of the chip idle there (accepted
 // as for the PnP kernel: DESIGN.md).
 #include "common.h"
 #include "feat.h"
+#include "stereo.h"
 
 #define FEAT_TILE 16
 #define FEAT_SEL_BLOCK 512
@@ -392,6 +399,120 @@ __global__ __launch_bounds__(256) void feat_points_kernel(const float *__restric
     pts[3 * row] = X; pts[3 * row + 1] = Y; pts[3 * row + 2] = Z;
 }
 
+// ---- sparse stereo -------------------------------------------------------------------------------------------------
+#define STEREO_WIN_STRIDE 16
+#define STEREO_STRIP_STRIDE 272    // >= STEREO_STRIP_W
+#define STEREO_NO_KEY 0x7fffffff
+
+struct StereoParams { int min_disparity, max_disparity, uniqueness, lr_tolerance; };
+
+__device__ __forceinline__ int32_t stereo_wave_min(int32_t v) {
+#pragma unroll
+    for (int o = 32; o >= 1; o >>= 1) { const int32_t w = __shfl_xor(v, o, 64); v = w < v ? w : v; }
+    return v;
+}
+
+// The costs of the window against the `count` windows of the strip, entry i for the disparity d_lo + i, into s_cost; the
+// wave's smallest key.  Window i of the strip starts at its column i, or at count - 1 - i when `mirrored` (the right strip:
+// a larger disparity lies further left).
+__device__ __forceinline__ int32_t stereo_search(const uint8_t *s_win, const uint8_t *s_strip, int count, int d_lo, bool mirrored,
+                                                 int32_t *s_cost, int lane) {
+    int w[STEREO_WIN_H * STEREO_WIN_W];
+#pragma unroll
+    for (int e = 0; e < STEREO_WIN_H * STEREO_WIN_W; ++e) w[e] = s_win[(e / STEREO_WIN_W) * STEREO_WIN_STRIDE + e % STEREO_WIN_W];
+    int32_t best = STEREO_NO_KEY;
+    for (int i = lane; i < count; i += 64) {
+        const uint8_t *p = s_strip + (mirrored ? count - 1 - i : i);
+        int32_t cost = 0;
+#pragma unroll
+        for (int e = 0; e < STEREO_WIN_H * STEREO_WIN_W; ++e) {
+            const int diff = w[e] - (int)p[(e / STEREO_WIN_W) * STEREO_STRIP_STRIDE + e % STEREO_WIN_W];
+            cost += diff * diff;
+        }
+        s_cost[i] = cost;
+        const int32_t key = stereo_key(cost, d_lo + i);
+        best = key < best ? key : best;
+    }
+    return stereo_wave_min(best);
+}
+
+// rows v - 1 .. v + 1, columns x0 .. x0 + width - 1 of an image into LDS rows of `stride` bytes
+__device__ __forceinline__ void stereo_stage(const uint8_t *img, int W, int v, int x0, int width, uint8_t *s, int stride, int lane) {
+    for (int e = lane; e < STEREO_WIN_H * width; e += 64) {
+        const int r = e / width, x = e % width;
+        s[r * stride + x] = img[(int64_t)(v - STEREO_HALF_H + r) * W + x0 + x];
+    }
+}
+
+__global__ __launch_bounds__(64) void feat_stereo_kernel(const uint8_t *__restrict__ left, const uint8_t *__restrict__ right,
+                                                         const int64_t *__restrict__ off, const int32_t *__restrict__ hw, FeatKeypoints K,
+                                                         const double *__restrict__ cams, StereoParams P, double *__restrict__ disparity,
+                                                         int32_t *__restrict__ status, int32_t *__restrict__ best, double *__restrict__ pts) {
+    __shared__ uint8_t s_win[STEREO_WIN_H * STEREO_WIN_STRIDE];
+    __shared__ uint8_t s_strip[STEREO_WIN_H * STEREO_STRIP_STRIDE];
+    __shared__ int32_t s_cost[STEREO_MAX_RANGE];
+    const int c = blockIdx.y, lane = threadIdx.x;
+    int64_t row;
+    if (!feat_keypoint_row(K, c, blockIdx.x, &row)) return;
+    const FeatImage im = feat_image(off, hw, c);
+    const int W = im.W, u = K.kp[2 * row], v = K.kp[2 * row + 1];
+    int st = STEREO_ACCEPTED, ds = -1, d_lo = 0, d_hi = 0;
+    int32_t ca = -1, cb = -1, cc = -1;
+    // every branch below is taken by the whole wave: u, v and the reduced keys are the same in all lanes
+    if (!stereo_inside(u, v, im.H, W)) st = STEREO_OUTSIDE;
+    else if (!stereo_range(u, P.min_disparity, P.max_disparity, &d_lo, &d_hi)) st = STEREO_NO_RANGE;
+    else {
+        const uint8_t *L = left + im.base, *R = right + im.base;
+        const int count = d_hi - d_lo + 1;                 // 3 .. 257
+        stereo_stage(L, W, v, u - STEREO_HALF_W, STEREO_WIN_W, s_win, STEREO_WIN_STRIDE, lane);
+        // columns u - d_hi - 7 >= 0 .. u - d_lo + 7 <= W - 1
+        stereo_stage(R, W, v, u - d_hi - STEREO_HALF_W, count - 1 + STEREO_WIN_W, s_strip, STEREO_STRIP_STRIDE, lane);
+        __syncthreads();
+        const int32_t key = stereo_search(s_win, s_strip, count, d_lo, true, s_cost, lane);
+        __syncthreads();
+        ds = stereo_key_d(key);
+        cb = stereo_key_cost(key);
+        if (ds > d_lo) ca = s_cost[ds - 1 - d_lo];
+        if (ds < d_hi) cc = s_cost[ds + 1 - d_lo];
+        if (ds == d_lo || ds == d_hi) st = STEREO_EDGE;
+        else {
+            int32_t second = STEREO_NO_KEY;
+            for (int i = lane; i < count; i += 64) {
+                const int dd = d_lo + i - ds;
+                if (dd >= 2 || dd <= -2) second = s_cost[i] < second ? s_cost[i] : second;
+            }
+            second = stereo_wave_min(second);
+            if (second != STEREO_NO_KEY && stereo_not_unique(second, cb, P.uniqueness)) st = STEREO_NOT_UNIQUE;
+            else if (P.lr_tolerance >= 0) {
+                // back from the right column ur: its window is window d_hi - ds of the strip, the left strip takes the strip's place
+                const int ur = u - ds, e_hi = stereo_range_back(ur, W, P.max_disparity), count2 = e_hi - d_lo + 1;      // ds in it
+                uint8_t wv = 0;
+                if (lane < STEREO_WIN_H * STEREO_WIN_W)
+                    wv = s_strip[(lane / STEREO_WIN_W) * STEREO_STRIP_STRIDE + d_hi - ds + lane % STEREO_WIN_W];
+                __syncthreads();                           // the strip and the costs have been read
+                if (lane < STEREO_WIN_H * STEREO_WIN_W) s_win[(lane / STEREO_WIN_W) * STEREO_WIN_STRIDE + lane % STEREO_WIN_W] = wv;
+                // columns ur + d_lo - 7 >= 1 (ds < d_hi <= u - 7) .. ur + e_hi + 7 <= W - 1
+                stereo_stage(L, W, v, ur + d_lo - STEREO_HALF_W, count2 - 1 + STEREO_WIN_W, s_strip, STEREO_STRIP_STRIDE, lane);
+                __syncthreads();
+                const int es = stereo_key_d(stereo_search(s_win, s_strip, count2, d_lo, false, s_cost, lane));
+                const int apart = es > ds ? es - ds : ds - es;
+                if (apart > P.lr_tolerance) st = STEREO_LEFT_RIGHT;
+            }
+        }
+    }
+    if (lane != 0) return;
+    double d = NAN, p[3] = {NAN, NAN, NAN};
+    if (st == STEREO_ACCEPTED) {
+        const double *cam = cams + 5 * c;
+        d = stereo_parabola(ds, ca, cb, cc);
+        stereo_point(u, v, d, cam[0], cam[1], cam[2], cam[3], cam[4], p);
+    }
+    disparity[row] = d;
+    status[row] = st;
+    if (best) { best[4 * row] = ds; best[4 * row + 1] = ca; best[4 * row + 2] = cb; best[4 * row + 3] = cc; }
+    pts[3 * row] = p[0]; pts[3 * row + 1] = p[1]; pts[3 * row + 2] = p[2];
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------
 static StreamScratch g_feat_scratch;
 
@@ -487,6 +608,29 @@ static void feat_launch_points(const float *depth, const int64_t *off, const int
                                const double *cams, double *pts, hipStream_t st) {
     if (most > 0)
         hipLaunchKernelGGL(feat_points_kernel, dim3((unsigned)ceil_div64(most, 256), (unsigned)n), dim3(256), 0, st, depth, off, hw, K, cams, pts);
+}
+
+static int feat_stereo_checks(const StereoParams &P, const double *h_cameras, int n) {
+    ARG_CHECK(P.min_disparity >= 1 && P.min_disparity <= P.max_disparity && P.max_disparity <= STEREO_MAX_DISPARITY,
+              "1 <= min_disparity <= max_disparity <= 255 is required");
+    ARG_CHECK(P.uniqueness >= 0 && P.uniqueness <= 100, "uniqueness must be in [0, 100] percent");
+    ARG_CHECK(P.lr_tolerance >= -1 && P.lr_tolerance <= 255, "lr_tolerance must be in [-1, 255]");
+    ARG_CHECK(h_cameras != nullptr, "h_cameras is required");
+    for (int c = 0; c < n; ++c) {
+        const double *cam = h_cameras + 5 * c;
+        ARG_CHECK(isfinite(cam[0]) && isfinite(cam[1]) && isfinite(cam[2]) && isfinite(cam[3]) && isfinite(cam[4]),
+                  "a stereo camera (fx, fy, cx, cy, baseline) must be finite");
+        ARG_CHECK(cam[0] > 0.0 && cam[1] > 0.0 && cam[4] > 0.0, "fx, fy and the baseline must be positive");
+    }
+    return CSLAM_OK;
+}
+
+static void feat_launch_stereo(const uint8_t *left, const uint8_t *right, const int64_t *off, const int32_t *hw, int n, const FeatKeypoints &K,
+                               int64_t most, const double *cams, const StereoParams &P, double *disparity, int32_t *status, int32_t *best,
+                               double *pts, hipStream_t st) {
+    if (most > 0)
+        hipLaunchKernelGGL(feat_stereo_kernel, dim3((unsigned)most, (unsigned)n), dim3(64), 0, st, left, right, off, hw, K, cams, P, disparity,
+                           status, best, pts);
 }
 
 CSLAM_API int cslam_feat_gray_dev(const uint8_t *d_src, const int64_t *d_src_off, const int64_t *d_off, const int32_t *d_hw, int n,
@@ -597,6 +741,71 @@ CSLAM_API int cslam_feat_extract_dev(const uint8_t *d_src, const int64_t *d_src_
     FeatKeypoints K = {d_kp, nullptr, d_count, max_features};
     feat_launch_describe(gray, d_off, d_hw, n, K, max_features, d_bins, d_desc, st);
     feat_launch_points(d_depth, d_off, d_hw, n, K, max_features, d_cameras, d_points, st);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_stereo_dev(const uint8_t *d_left, const uint8_t *d_right, const int64_t *d_off, const int32_t *d_hw, int n,
+                                    const int32_t *d_kp, const int64_t *d_kp_off, const double *d_cameras, int min_disparity,
+                                    int max_disparity, int uniqueness, int lr_tolerance, double *d_disparity, int32_t *d_status,
+                                    int32_t *d_best, double *d_points, const int64_t *h_off, const int32_t *h_hw, const int64_t *h_kp_off,
+                                    const double *h_cameras, void *stream) {
+    FeatShape sh;
+    RaggedShape ks;
+    const StereoParams P = {min_disparity, max_disparity, uniqueness, lr_tolerance};
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_kp_shape(h_kp_off, n, &ks))) return rc;
+    if ((rc = feat_stereo_checks(P, h_cameras, n))) return rc;
+    ARG_CHECK(d_left && d_right && d_off && d_hw && d_kp && d_kp_off && d_cameras && d_disparity && d_status && d_best && d_points,
+              "NULL argument");
+    PTR_DEVICE(d_left);
+    FeatKeypoints K = {d_kp, d_kp_off, nullptr, 0};
+    feat_launch_stereo(d_left, d_right, d_off, d_hw, n, K, ks.largest, d_cameras, P, d_disparity, d_status, d_best, d_points,
+                       (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_extract_stereo_dev(const uint8_t *d_left, const int64_t *d_left_off, const uint8_t *d_right,
+                                            const int64_t *d_right_off, const int64_t *d_off, const int32_t *d_hw, const double *d_cameras,
+                                            int n, double quality_level, int min_distance, int border, int max_features, int min_disparity,
+                                            int max_disparity, int uniqueness, int lr_tolerance, int32_t *d_count, int32_t *d_kp,
+                                            int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc, double *d_points, double *d_disparity,
+                                            int32_t *d_status, const int64_t *h_left_off, const int64_t *h_right_off, const int64_t *h_off,
+                                            const int32_t *h_hw, const double *h_cameras, void *stream) {
+    FeatShape sh;
+    const StereoParams P = {min_disparity, max_disparity, uniqueness, lr_tolerance};
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_src_check(h_left_off, h_off, n))) return rc;
+    if ((rc = feat_src_check(h_right_off, h_off, n))) return rc;
+    if ((rc = feat_select_checks(quality_level, min_distance, border, max_features))) return rc;
+    if ((rc = feat_stereo_checks(P, h_cameras, n))) return rc;
+    ARG_CHECK(d_left && d_left_off && d_right && d_right_off && d_off && d_hw && d_cameras && d_count && d_kp && d_resp && d_bins && d_desc &&
+                  d_points && d_disparity && d_status,
+              "NULL argument");
+    PTR_DEVICE(d_left);
+    hipStream_t st = (hipStream_t)stream;
+    FeatSelScratch s;
+    uint8_t *gray_l, *gray_r;
+    int32_t *R, *rmax;
+    auto layout = [&](Carver &cv) {
+        gray_l = cv.take<uint8_t>((size_t)sh.px.total);
+        gray_r = cv.take<uint8_t>((size_t)sh.px.total);
+        R = cv.take<int32_t>((size_t)sh.px.total);
+        rmax = cv.take<int32_t>((size_t)n);
+        feat_sel_carve(cv, (size_t)sh.px.total, &s);
+    };
+    SCRATCH_CARVE(g_feat_scratch, st, (size_t)1 << 20, layout);
+    feat_launch_gray(d_left, d_left_off, d_off, n, sh, gray_l, st);
+    feat_launch_gray(d_right, d_right_off, d_off, n, sh, gray_r, st);
+    if ((rc = feat_launch_response(gray_l, d_off, d_hw, n, sh, R, rmax, st))) return rc;
+    feat_launch_select(R, rmax, nullptr, nullptr, d_off, d_hw, n, sh, quality_level, min_distance, border, max_features, s, d_count, d_kp,
+                       d_resp, st);                        // a stereo frame has no depth image, so no mask
+    FeatKeypoints K = {d_kp, nullptr, d_count, max_features};
+    feat_launch_describe(gray_l, d_off, d_hw, n, K, max_features, d_bins, d_desc, st);
+    feat_launch_stereo(gray_l, gray_r, d_off, d_hw, n, K, max_features, d_cameras, P, d_disparity, d_status, nullptr, d_points, st);
     HIP_TRY(hipGetLastError());
     return CSLAM_OK;
 }

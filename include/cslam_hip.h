@@ -734,7 +734,7 @@ int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d_points_fr
  *   k / 8 quarter turns (x, y) -> (-y, x).  Bit i = blur(p_i) < blur(q_i), bit i mod 8 of byte i / 8.
  * Points (generateKeypoints3D): depth float32 metres of the image's size, valid iff finite and > 0; in float64
  *   X = ((u - cx) d) / fx, Y = ((v - cy) d) / fy, Z = d; a keypoint without valid depth gives a NaN row.
- * Out of scope: the stereo handler, depth images smaller than the colour image, scale pyramids, sub-pixel refinement. */
+ * Out of scope: depth images smaller than the colour image, scale pyramids, sub-pixel refinement. */
 /* cslam_feat_gray_dev -- the grey conversion of rgbd_handler.cpp:266-312.  d_src uint8, image c = the bytes
  *   [d_src_off[c], d_src_off[c + 1]): H W of them (one channel) or 3 H W (B, G, R interleaved).  d_gray uint8 [total pixels]. */
 int cslam_feat_gray_dev(const uint8_t *d_src, const int64_t *d_src_off, const int64_t *d_off, const int32_t *d_hw, int n,
@@ -772,6 +772,63 @@ int cslam_feat_extract_dev(const uint8_t *d_src, const int64_t *d_src_off, const
                            int max_features, int depth_as_mask, int32_t *d_count, int32_t *d_kp, int32_t *d_resp, int32_t *d_bins,
                            uint8_t *d_desc, double *d_points, const int64_t *h_src_off, const int64_t *h_off, const int32_t *h_hw,
                            void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Stereo keyframes: sparse disparity at the keypoints (feat_stereo_kernel in csrc/feat.hip, the rules in csrc/stereo.h).
+ * StereoHandler inherits compute_local_descriptors (rgbd_handler.cpp:266-312) unchanged; a stereo frame differs only in
+ * where generateKeypoints3D (rgbd_handler.cpp:309) gets depth: the SensorData is built from a left and a right rectified
+ * image and a stereo camera model (stereo_handler.cpp:148-227), rtabmap looks each keypoint up in the right image along
+ * its row and triangulates from the disparity.  There is no depth image and so no depth mask; a keypoint without a
+ * correspondence keeps a NaN point.  Parity with rtabmap's Stereo::computeCorrespondences is unpinned, as for the features
+ * above.  What is pinned is the rule stated here: integer arithmetic up to one float64 division, so the GPU, csrc/stereo.h
+ * on the host and tests/stereo_reference.py agree bit for bit.
+ *
+ * Inputs per frame: left and right grey images L, R, uint8, the same H x W, rectified (a point of left column u and
+ *   disparity d lies at right column u - d of the same row); keypoints (u, v) int32 in the left image; a camera row of five
+ *   float64 (fx, fy, cx, cy, baseline): baseline in metres and > 0, the same principal point in both images.
+ * Parameters: 1 <= min_disparity <= max_disparity <= 255 (defaults 1, 128); uniqueness in [0, 100] percent (15);
+ *   lr_tolerance in [-1, 255] (1), -1 = no left-right check.  Constants: window half-width 7, half-height 1 (15 x 3).
+ * Cost: C(d) = sum over dy = -1 .. 1, dx = -7 .. 7 of (L[v + dy, u + dx] - R[v + dy, u - d + dx])^2, an int32
+ *   <= 45 * 255^2 = 2926125 < 2^22; (C << 9) | d is a 31-bit key whose minimum is the best cost, the lowest d among equals.
+ * Status, the first rule that applies:
+ *   1 outside     not (7 <= u <= W - 8 and 1 <= v <= H - 2).
+ *   2 no range    D_lo = min_disparity - 1, D_hi = min(max_disparity + 1, u - 7), and D_hi - D_lo < 2.
+ *   3 edge        d* = argmin C over [D_lo, D_hi], the lowest d on ties, is D_lo or D_hi: the disparity lies outside
+ *                 [min, max] or the parabola lacks a neighbour.  Constant images land here.
+ *   4 not unique  S = min C(d) over the range with |d - d*| >= 2 exists and S * 100 <= C(d*) * (100 + uniqueness) in int64.
+ *   5 left-right  only when lr_tolerance >= 0: ur = u - d*, C'(e) = sum (R[v + dy, ur + dx] - L[v + dy, ur + e + dx])^2 over
+ *                 e in [D_lo, min(max_disparity + 1, W - 8 - ur)], e* = argmin C', the lowest e on ties, and
+ *                 |e* - d*| > lr_tolerance.
+ *   0 accepted    otherwise.
+ * Disparity (status 0, otherwise NaN): a = C(d* - 1), b = C(d*), c = C(d* + 1), den = a - 2 b + c > 0 (a > b by the tie
+ *   rule, c >= b); disparity = (double)d* + (double)(a - c) / (double)(2 den): one division, one addition.
+ * Point (status 0, otherwise a NaN row): Z = (baseline fx) / disparity, X = ((u - cx) Z) / fx, Y = ((v - cy) Z) / fy.
+ * Diagnostic: best int32 [rows, 4] = (d*, a, b, c); d* = -1 for status 1 and 2; each of a, b, c is -1 where that disparity
+ *   lies outside [D_lo, D_hi].
+ * Out of scope: unrectified pairs, different principal points in the two images, pyramids, rtabmap's optical-flow variant
+ *   of the correspondence search, Vis/MinDepth and Vis/MaxDepth. */
+/* cslam_feat_stereo_dev -- the depth of generateKeypoints3D (rgbd_handler.cpp:309) for a stereo frame
+ *   (stereo_handler.cpp:148-227): d_left, d_right uint8 [total pixels] grey in the ragged layout of the feature section
+ *   (d_off, d_hw, h_off, h_hw), keypoints d_kp int32 [total, 2] with d_kp_off int64 [n + 1] (h_kp_off: the same on the
+ *   host), d_cameras float64 [n, 5] (h_cameras: the same on the host, required: it is checked before the launch) ->
+ *   d_disparity float64 [total], d_status int32 [total], d_best int32 [total, 4], d_points float64 [total, 3]. */
+int cslam_feat_stereo_dev(const uint8_t *d_left, const uint8_t *d_right, const int64_t *d_off, const int32_t *d_hw, int n,
+                          const int32_t *d_kp, const int64_t *d_kp_off, const double *d_cameras, int min_disparity, int max_disparity,
+                          int uniqueness, int lr_tolerance, double *d_disparity, int32_t *d_status, int32_t *d_best, double *d_points,
+                          const int64_t *h_off, const int32_t *h_hw, const int64_t *h_kp_off, const double *h_cameras, void *stream);
+/* cslam_feat_extract_stereo_dev -- compute_local_descriptors for a stereo frame (rgbd_handler.cpp:266-312 with the depth
+ *   of :309 from stereo_handler.cpp:148-227) on one stream with no host wait in between: grey of left and right, response
+ *   and selection on the left without a mask, bins and descriptors on the left, the stereo rule.  d_left / d_right with
+ *   d_left_off / d_right_off as d_src / d_src_off of cslam_feat_gray_dev: the two sides of a frame have the same H x W but
+ *   may differ in channels.  Outputs as cslam_feat_extract_dev, plus d_disparity float64 and d_status int32
+ *   [n, max_features]. */
+int cslam_feat_extract_stereo_dev(const uint8_t *d_left, const int64_t *d_left_off, const uint8_t *d_right, const int64_t *d_right_off,
+                                  const int64_t *d_off, const int32_t *d_hw, const double *d_cameras, int n, double quality_level,
+                                  int min_distance, int border, int max_features, int min_disparity, int max_disparity, int uniqueness,
+                                  int lr_tolerance, int32_t *d_count, int32_t *d_kp, int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc,
+                                  double *d_points, double *d_disparity, int32_t *d_status, const int64_t *h_left_off,
+                                  const int64_t *h_right_off, const int64_t *h_off, const int32_t *h_hw, const double *h_cameras,
+                                  void *stream);
 
 /* Winograd F(2x2, 3x3) transforms for the 3x3 / stride 1 / pad 1 convolutions of the extractor backbone
  * (the VGG-16 trunk built at cslam/vpr/netvlad.py:163-171; the reference runs it through torch's direct

@@ -1,5 +1,7 @@
 """Times of the keyframe features (csrc/feat.hip) by HIP events: one 480 x 640 BGR frame and a batch of 16, each stage
-apart (grey, response, selection, bins and descriptors, points) and the whole chain.  Prints one JSON line.
+apart (grey, response, selection, bins and descriptors, points) and the whole chain; then the stereo leg on the same
+frames with a right image 12 columns apart: the stereo kernel alone on the selected keypoints and the chained stereo
+frame.  Prints one JSON line.
 
     python tools/perf_visual_features.py [--reps 20]
 """
@@ -64,6 +66,15 @@ def main():
         k_off = offsets([mf] * batch)                      # the staged entries take the rows as ragged: here all mf per image
         t_ko = to_dev(k_off, dev)
         h = (host(off), host(hw))
+        # the stereo leg: the right image is the left one seen 12 columns further left (disparity 12 everywhere)
+        rights = [np.ascontiguousarray(np.roll(i, -12, axis=1)) for i in imgs]
+        t_right = to_dev(np.concatenate([i.reshape(-1) for i in rights]), dev)
+        t_gray_r = torch.zeros(total, dtype=torch.uint8, device=dev)
+        scam = np.tile(np.array([525.0, 525.0, W / 2 - 0.5, H / 2 - 0.5, 0.12]), (batch, 1))
+        t_scam = to_dev(scam, dev)
+        t_disp = torch.zeros((batch, mf), dtype=torch.float64, device=dev)
+        t_status = torch.zeros((batch, mf), dtype=torch.int32, device=dev)
+        t_best = torch.zeros((batch, mf, 4), dtype=torch.int32, device=dev)
 
         def gray():
             _lib.check(lib.cslam_feat_gray_dev(t_src.data_ptr(), t_so.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch, t_gray.data_ptr(),
@@ -91,6 +102,23 @@ def main():
                                                   t_resp.data_ptr(), t_bins.data_ptr(), t_desc.data_ptr(), t_pts.data_ptr(), host(src_off), *h,
                                                   stream()))
 
+        def gray_right():
+            _lib.check(lib.cslam_feat_gray_dev(t_right.data_ptr(), t_so.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch,
+                                               t_gray_r.data_ptr(), host(src_off), *h, stream()))
+
+        def stereo():
+            _lib.check(lib.cslam_feat_stereo_dev(t_gray.data_ptr(), t_gray_r.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch,
+                                                 t_kp.data_ptr(), t_ko.data_ptr(), t_scam.data_ptr(), 1, 128, 15, 1, t_disp.data_ptr(),
+                                                 t_status.data_ptr(), t_best.data_ptr(), t_pts.data_ptr(), *h, host(k_off), host(scam),
+                                                 stream()))
+
+        def stereo_chain():
+            _lib.check(lib.cslam_feat_extract_stereo_dev(t_src.data_ptr(), t_so.data_ptr(), t_right.data_ptr(), t_so.data_ptr(),
+                                                         t_off.data_ptr(), t_hw.data_ptr(), t_scam.data_ptr(), batch, 0.001, 7, 19, mf, 1, 128,
+                                                         15, 1, t_cnt.data_ptr(), t_kp.data_ptr(), t_resp.data_ptr(), t_bins.data_ptr(),
+                                                         t_desc.data_ptr(), t_pts.data_ptr(), t_disp.data_ptr(), t_status.data_ptr(),
+                                                         host(src_off), host(src_off), *h, host(scam), stream()))
+
         def timed(fn):
             for _ in range(3):
                 fn()
@@ -112,6 +140,12 @@ def main():
             t_kp[:, :, 1].clamp_(18, H - 19)
         res.update({"describe_ms": timed(describe), "points_ms": timed(points), "chain_ms": timed(chain)})
         res["keypoints_per_image"] = round(float(t_cnt.cpu().numpy().mean()), 1)
+        gray_right()
+        res.update({"stereo_ms": timed(stereo), "stereo_chain_ms": timed(stereo_chain)})
+        n_st = t_cnt.cpu().numpy()
+        st = t_status.cpu().numpy()
+        res["stereo_keypoints_per_image"] = round(float(n_st.mean()), 1)
+        res["stereo_accepted_per_image"] = round(float(np.mean([(st[c, :n_st[c]] == 0).sum() for c in range(batch)])), 1)
         out["batch_%d" % batch] = res
     print(json.dumps(out))
 

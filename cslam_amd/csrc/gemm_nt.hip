@@ -152,11 +152,18 @@ __global__ __launch_bounds__(256) void pca_epilogue_kernel(const float *__restri
     for (int d = threadIdx.x; d < M; d += blockDim.x) out[(size_t)b * M + d] /= den;
 }
 
-// the same epilogue for the pair products: their power-of-two input scale is recomputed from the max |x| slot
+// the same epilogue for the pair products: their power-of-two input scale is recomputed from the max |x| slot.
+// KEEP: the row's results stay in registers between the sum of squares and the division (M <= 4096: four float4 per thread; the
+// split count is the constant S = 8 of PCA_PAIR_SPLITS, so all 32 partial loads of a thread are in flight before the first sum) and
+// `out` is written once; otherwise they are staged in `out` and read back.  Both forms add in the same order.
+template <bool KEEP>
 __global__ __launch_bounds__(256) void pca_epilogue_pairs_kernel(const float *__restrict__ part, int S, int N, int M,
                                                                  const float *__restrict__ mean_proj,
                                                                  const float *__restrict__ inv_scale, float *__restrict__ out,
                                                                  const unsigned *__restrict__ amax, float a_given, float inv_sw) {
+    // every product and sum below is rounded on its own in both forms: which of x^2 + y^2 + ... would become an fma otherwise
+    // depends on the shape of the code around it, and the two forms (and the rows of earlier builds) must agree bit for bit
+#pragma clang fp contract(off)
     __shared__ float red[16];
     const float a = fminf(fmaxf(amax ? __uint_as_float(*amax) : a_given, 1e-30f), 1e30f);
     int e;
@@ -167,7 +174,7 @@ __global__ __launch_bounds__(256) void pca_epilogue_pairs_kernel(const float *__
     typedef float pf4 __attribute__((ext_vector_type(4)));
     // four consecutive outputs per thread (M is a multiple of 128 here), the partials of a split 16 bytes at a time, four
     // splits in flight: the scalar loop was a chain of S dependent-latency loads per output (0.11 ms per 256 rows)
-    for (int d = 4 * threadIdx.x; d < M; d += 4 * blockDim.x) {
+    auto value = [&](int d) {
         pf4 v = (pf4)(0.0f);
         int s = 0;
         for (; s + 4 <= S; s += 4) {
@@ -179,8 +186,47 @@ __global__ __launch_bounds__(256) void pca_epilogue_pairs_kernel(const float *__
         v *= ps;
         if (mean_proj) v -= *(const pf4 *)(mean_proj + d);
         if (inv_scale) v *= *(const pf4 *)(inv_scale + d);
-        *(pf4 *)(out + (size_t)b * M + d) = v;
-        ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        return v;
+    };
+    pf4 keep[4];
+    if (KEEP) {
+        // S == 8 here.  Columns past M are read at the row's last four (M >= 128) and left out of the sum and the store: no branch
+        // between the loads, so the 32 of them are in flight together.
+        pf4 p[4][8], mp[4], is[4];
+        int dc[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int d = 4 * threadIdx.x + 1024 * i;
+            dc[i] = d < M ? d : M - 4;
+#pragma unroll
+            for (int s = 0; s < 8; ++s) p[i][s] = *(const pf4 *)(part + ((size_t)s * N + b) * M + dc[i]);
+        }
+        if (mean_proj) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) mp[i] = *(const pf4 *)(mean_proj + dc[i]);
+        }
+        if (inv_scale) {
+#pragma unroll
+            for (int i = 0; i < 4; ++i) is[i] = *(const pf4 *)(inv_scale + dc[i]);
+        }
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            pf4 v = (pf4)(0.0f);
+            v = (((v + p[i][0]) + p[i][1]) + p[i][2]) + p[i][3];
+            v = (((v + p[i][4]) + p[i][5]) + p[i][6]) + p[i][7];
+            v *= ps;
+            if (mean_proj) v -= mp[i];
+            if (inv_scale) v *= is[i];
+            keep[i] = v;
+            const float q = v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+            if (4 * (int)threadIdx.x + 1024 * i < M) ss += q;
+        }
+    } else {
+        for (int d = 4 * threadIdx.x; d < M; d += 4 * blockDim.x) {
+            const pf4 v = value(d);
+            *(pf4 *)(out + (size_t)b * M + d) = v;
+            ss += v.x * v.x + v.y * v.y + v.z * v.z + v.w * v.w;
+        }
     }
 #pragma unroll
     for (int off = 32; off >= 1; off >>= 1) ss += __shfl_xor(ss, off, 64);
@@ -190,10 +236,18 @@ __global__ __launch_bounds__(256) void pca_epilogue_pairs_kernel(const float *__
     for (int w = 0; w < (int)(blockDim.x >> 6); ++w) t += red[w];
     const float nrm = sqrtf(t);
     const float den = nrm == 0.0f ? 1.0f : nrm;
-    for (int d = 4 * threadIdx.x; d < M; d += 4 * blockDim.x) {
-        pf4 v = *(pf4 *)(out + (size_t)b * M + d);
-        v /= den;
-        *(pf4 *)(out + (size_t)b * M + d) = v;
+    if (KEEP) {
+#pragma unroll
+        for (int i = 0; i < 4; ++i) {
+            const int d = 4 * threadIdx.x + 1024 * i;
+            if (d < M) *(pf4 *)(out + (size_t)b * M + d) = keep[i] / den;
+        }
+    } else {
+        for (int d = 4 * threadIdx.x; d < M; d += 4 * blockDim.x) {
+            pf4 v = *(pf4 *)(out + (size_t)b * M + d);
+            v /= den;
+            *(pf4 *)(out + (size_t)b * M + d) = v;
+        }
     }
 }
 
@@ -353,6 +407,23 @@ __global__ __launch_bounds__(256) void pca_absmax_kernel(const float *__restrict
     if ((threadIdx.x & 63) == 0) atomicMax(slot, __float_as_uint(m));
 }
 
+// pair rows A2 -> split products -> epilogue (`slot`: the device's max |x|, or NULL and the bound `x_bound` the rows were scaled with)
+static int pca_pairs_product(const void *A2, const unsigned *slot, float x_bound, const void *d_W2, float inv_sw, int S,
+                             const float *d_mean_proj, const float *d_inv_scale, int B, int Din, int Dout, float *part,
+                             float *d_out, hipStream_t st) {
+    const int rc = cslam_pair_gemm_launch(A2, d_W2, S, B, Din / S, Dout, part, st);
+    if (rc != CSLAM_OK) return rc;
+    // the input scale is only known on the device: the epilogue undoes it from the same slot
+    if (Dout <= 4096 && S == 8)
+        hipLaunchKernelGGL(pca_epilogue_pairs_kernel<true>, dim3(B), dim3(256), 0, st, part, S, B, Dout, d_mean_proj, d_inv_scale,
+                           d_out, slot, x_bound, inv_sw);
+    else
+        hipLaunchKernelGGL(pca_epilogue_pairs_kernel<false>, dim3(B), dim3(256), 0, st, part, S, B, Dout, d_mean_proj, d_inv_scale,
+                           d_out, slot, x_bound, inv_sw);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
 // x_bound > 0: a known bound of max |x| (e.g. 1 for L2-normalised VLAD vectors) instead of a pass over x.
 // out = normalize_row(((x - 0) W^T - mean_proj) * inv_scale) with W given as pairs: d_W2 [S][Dout][Din / S / 32][hi 32 | lo 32] of
 // sW W (`pca_pair_weights`), inv_sw = 1 / sW.  Workspaces (A2, partials, the max |x| slot) live in the grow-only scratch.
@@ -383,11 +454,24 @@ CSLAM_API int cslam_pca_project_pairs_dev(const float *d_x, int64_t ldx, float x
     hipLaunchKernelGGL(pca_pairs_rows_kernel, dim3((unsigned)ceil_div64((int64_t)B * (Din / 4), 256)), dim3(256), 0, st, d_x, ldx, B,
                        Din, S, slot, x_bound, A2);
     HIP_TRY(hipGetLastError());
-    const int rc = cslam_pair_gemm_launch(A2, d_W2, S, B, Din / S, Dout, part, st);
-    if (rc != CSLAM_OK) return rc;
-    // the input scale is only known on the device: the epilogue undoes it from the same slot
-    hipLaunchKernelGGL(pca_epilogue_pairs_kernel, dim3(B), dim3(256), 0, st, part, S, B, Dout, d_mean_proj, d_inv_scale, d_out, slot,
-                       x_bound, inv_sw);
-    HIP_TRY(hipGetLastError());
-    return CSLAM_OK;
+    return pca_pairs_product(A2, slot, x_bound, d_W2, inv_sw, S, d_mean_proj, d_inv_scale, B, Din, Dout, part, d_out, st);
+}
+
+// The projection of rows that already are pairs: d_A2 [S][B][Din / S / 32][hi 32 | lo 32] fp16 of s x, s the power of two that
+// `x_bound` (> 0, the bound the producer scaled with) gives -- what `cslam_vlad_aggregate_nhwc_pairs_dev` writes (heads.hip).
+// The products, the split sums and the epilogue are those of cslam_pca_project_pairs_dev: the same bits from the same rows.
+CSLAM_API int cslam_pca_project_from_pairs_dev(const void *d_A2, float x_bound, const void *d_W2, float inv_sw, int S,
+                                               const float *d_mean_proj, const float *d_inv_scale, int B, int Din, int Dout,
+                                               float *d_out, void *stream) {
+    PTR_DEVICE(d_A2);
+    ARG_CHECK(d_A2 && d_W2 && d_out, "NULL argument");
+    ARG_CHECK(B >= 1 && S >= 1 && Din >= 32 * S && (Din % (32 * S)) == 0, "Din must be a multiple of 32 S");
+    ARG_CHECK(Dout >= 128 && (Dout % 128) == 0, "Dout must be a multiple of 128");
+    ARG_CHECK((uintptr_t)d_A2 % 16 == 0, "the pair rows must be 16-byte aligned");
+    ARG_CHECK(x_bound > 0.0f, "the bound the pair rows were scaled with must be given");
+    ARG_CHECK(inv_sw > 0.0f, "inv_sw must be positive");
+    hipStream_t st = (hipStream_t)stream;
+    int dev = 0; HIP_TRY(hipGetDevice(&dev));
+    SCRATCH_GET(g_part_c, char *, g_part_scratch, dev, stream, (size_t)S * B * Dout * 4, (size_t)64 << 20);
+    return pca_pairs_product(d_A2, nullptr, x_bound, d_W2, inv_sw, S, d_mean_proj, d_inv_scale, B, Din, Dout, (float *)g_part_c, d_out, st);
 }

@@ -13,6 +13,7 @@
 // per-image intermediates.  float32 arithmetic like the reference's torch float32 modules.
 #include <stdlib.h>
 #include "common.h"
+#include "pairs.h"
 #include <mutex>
 #include <vector>
 
@@ -390,9 +391,14 @@ typedef float vf32x16 __attribute__((ext_vector_type(16)));
 #define VM_AP 65                       // LDS row pitch of the assignment (and of the W block) in floats
 #define VM_PP 200                      // padded pixel count (even, >= P): LDS rows
 #define VM_LDS_FLOATS (VM_PP * VM_XS + VM_PP * VM_AP + 256 + VK + 8 * VK + 16)
+// PAIRS: the final store also writes the row as the fp16 hi / lo pairs the PCA projection multiplies (gemm_nt.hip: the layout and
+// the arithmetic of pca_pairs_rows_kernel on the float32 row, so the same bits) -- A2 [S][B][K C / S / 32][hi 32 | lo 32] of s v,
+// s the power of two from the bound a_given of max |v|, S = K >> kshift splits of whole clusters; `out` may then be NULL.
+template <bool PAIRS>
 __global__ __launch_bounds__(512) void vlad_mfma_kernel(const float *__restrict__ feat, const float *__restrict__ W,
                                                         const float *__restrict__ bias, const float *__restrict__ cent,
-                                                        int C, int P, float *__restrict__ out, int64_t ldo) {
+                                                        int C, int P, float *__restrict__ out, int64_t ldo,
+                                                        unsigned short *__restrict__ A2, int kshift, float a_given) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     float *xs = (float *)smem;                        // [VM_PP][VM_XS]
     float *a_lds = xs + VM_PP * VM_XS;                // [VM_PP][VM_AP] logits -> softmax -> a'; sweep 1: ws [VM_CS][VM_AP] lives here
@@ -645,6 +651,15 @@ __global__ __launch_bounds__(512) void vlad_mfma_kernel(const float *__restrict_
     const float gsum = (red[4 * VK] + red[4 * VK + 1]) + (red[4 * VK + 2] + red[4 * VK + 3]);
     const float gs = 1.0f / fmaxf(sqrtf(gsum), 1e-12f);
     float *o = out + (size_t)blockIdx.x * ldo;
+    float psc = 1.0f;
+    if (PAIRS) {                                                       // the input scale of pca_pairs_rows_kernel
+        const float a = fminf(fmaxf(a_given, 1e-30f), 1e30f);
+        int e;
+        (void)frexpf(16384.0f / a, &e);
+        psc = ldexpf(1.0f, e - 1);
+    }
+    const int kb = (C << kshift) >> 5;                                 // 128-byte blocks per pair row of a split
+    const bool odd = l31 & 1;
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
         const int sl = nslab - 1 - t;
@@ -653,7 +668,19 @@ __global__ __launch_bounds__(512) void vlad_mfma_kernel(const float *__restrict_
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int k = 32 * ct + (r & 3) + 8 * (r >> 2) + 4 * h;
-                o[(size_t)k * C + c] = vo[t][r] * sc[r] * gs;
+                const float val = vo[t][r] * sc[r] * gs;
+                if (!PAIRS || out) o[(size_t)k * C + c] = val;
+                if (PAIRS) {
+                    // element k C + c of the row = split k >> kshift, column cc of it; the 32 lanes of a half-wave hold one block's
+                    // 32 columns: neighbours exchange so that the even lane stores two hi halves and the odd lane two lo halves
+                    const float sv = val * psc;
+                    const unsigned mine = pack_pair(sv);
+                    const unsigned other = (unsigned)__builtin_amdgcn_update_dpp(0, (int)mine, 0xB1, 0xF, 0xF, true);   // lane ^ 1
+                    const unsigned word = odd ? ((other >> 16) | (mine & 0xffff0000u)) : ((mine & 0xffffu) | (other << 16));
+                    const int cc = (k & ((1 << kshift) - 1)) * C + c;
+                    const int64_t blk = ((int64_t)(k >> kshift) * gridDim.x + blockIdx.x) * kb + (cc >> 5);
+                    *(unsigned *)(A2 + blk * 64 + (odd ? 32 + l31 - 1 : l31)) = word;
+                }
             }
         }
     }
@@ -828,11 +855,11 @@ static int vlad_aggregate(const float *d_feat, const float *d_assign_w, const fl
             static DeviceOnce once;
             int once_dev;
             if (once.todo(&once_dev)) {
-                HIP_TRY(hipFuncSetAttribute((const void *)vlad_mfma_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
+                HIP_TRY(hipFuncSetAttribute((const void *)vlad_mfma_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
                 once.done(once_dev);
             }
-            hipLaunchKernelGGL(vlad_mfma_kernel, dim3(B), dim3(512), lds_m, (hipStream_t)stream, d_feat, d_assign_w, d_assign_b,
-                               d_centroids, C, P, d_out, ldo);
+            hipLaunchKernelGGL(vlad_mfma_kernel<false>, dim3(B), dim3(512), lds_m, (hipStream_t)stream, d_feat, d_assign_w, d_assign_b,
+                               d_centroids, C, P, d_out, ldo, (unsigned short *)nullptr, 0, 0.0f);
             HIP_TRY(hipGetLastError());
             return CSLAM_OK;
         }
@@ -890,6 +917,38 @@ CSLAM_API int cslam_vlad_aggregate_nhwc_dev(const float *d_feat, const float *d_
                                             const float *d_centroids, int B, int C, int P, int K,
                                             float *d_out, int64_t ldo, void *stream) {
     return vlad_aggregate(d_feat, d_assign_w, d_assign_b, d_centroids, B, C, P, K, d_out, ldo, stream, true);
+}
+
+// The matrix form with the pair rows of the projection written by its final store (vlad_mfma_kernel<true>): one pass over the
+// VLAD vector less in each direction than cslam_vlad_aggregate_nhwc_dev + the row kernel of cslam_pca_project_pairs_dev, which it
+// equals bit for bit.  d_A2 [S][B][K C / S / 32][hi 32 | lo 32] fp16; d_out [B][K C] (pitch ldo) or NULL.  Only the shapes of the
+// matrix form (C a multiple of 128 up to 512, 32 <= P <= 200), any B >= 1; S a power of two up to K (whole clusters per split).
+CSLAM_API int cslam_vlad_aggregate_nhwc_pairs_dev(const float *d_feat, const float *d_assign_w, const float *d_assign_b,
+                                                  const float *d_centroids, int B, int C, int P, int K, float x_bound, int S,
+                                                  void *d_A2, float *d_out, int64_t ldo, void *stream) {
+    PTR_DEVICE(d_feat);
+    ARG_CHECK(d_feat && d_assign_w && d_centroids && d_A2, "NULL argument");
+    ARG_CHECK(K == VK, "K must be 64 (reference: num_clusters=64, netvlad.py:176)");
+    ARG_CHECK(C >= VM_CS && C % VM_CS == 0 && C <= 4 * VM_CS && P <= VM_PP && P >= 32 && B >= 0,
+              "the pair-row form is the matrix kernel's: C a multiple of 128 up to 512, 32 <= P <= 200");
+    ARG_CHECK(S >= 1 && S <= VK && (S & (S - 1)) == 0, "S must be a power of two up to K");
+    ARG_CHECK(x_bound > 0.0f, "a bound of max |v| must be given (1 for the L2-normalised vector)");
+    ARG_CHECK((uintptr_t)d_A2 % 16 == 0, "the pair rows must be 16-byte aligned");
+    ARG_CHECK(!d_out || ldo >= (int64_t)K * C, "output pitch smaller than K*C");
+    if (B == 0) return CSLAM_OK;
+    int kshift = 0;
+    while ((S << kshift) < VK) ++kshift;
+    const size_t lds_m = (size_t)VM_LDS_FLOATS * 4;
+    static DeviceOnce once;
+    int once_dev;
+    if (once.todo(&once_dev)) {
+        HIP_TRY(hipFuncSetAttribute((const void *)vlad_mfma_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds_m));
+        once.done(once_dev);
+    }
+    hipLaunchKernelGGL(vlad_mfma_kernel<true>, dim3(B), dim3(512), lds_m, (hipStream_t)stream, d_feat, d_assign_w, d_assign_b,
+                       d_centroids, C, P, d_out, ldo, (unsigned short *)d_A2, kshift, x_bound);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
 }
 
 // ------------------------------------------------------------ CosPlace head ----

@@ -151,6 +151,53 @@ def pca_project(x, components, mean_proj, inv_scale, pairs=None, x_bound=0.0):
     return out
 
 
+VLAD_BOUND = 1.0 + 2.0 ** -20    # the VLAD vector is L2-normalised (netvlad.py:130): |v| <= 1, one ulp of slack
+
+
+def vlad_pairs_fit(feat, centroids, pairs):
+    """True when `vlad_aggregate_pairs` takes this channels-last map: the matrix form's shapes (C a multiple of 128 up to 512,
+    32 <= h w <= 200, 64 clusters), pair weights over whole clusters and a batch the pair projection takes."""
+    if pairs is None or feat.dim() != 4:
+        return False
+    B, Cc = feat.shape[:2]
+    P, K, S = feat.shape[2] * feat.shape[3], centroids.shape[0], pairs[0].shape[0]
+    return (B >= PCA_PAIR_MIN_BATCH and K == 64 and Cc % 128 == 0 and Cc <= 512 and 32 <= P <= 200 and S <= K and S & (S - 1) == 0
+            and feat.is_cuda and feat.dtype == torch.float32 and feat.is_contiguous(memory_format=torch.channels_last))
+
+
+def vlad_aggregate_pairs(feat, assign_w, assign_b, centroids, splits=PCA_PAIR_SPLITS, x_bound=VLAD_BOUND, keep_v=False):
+    """channels-last [B,C,h,w] -> (A2 [S, B, 64 C / S / 32, 64] float16, v [B, 64 C] or None): `vlad_aggregate` whose final store
+    writes the rows as the fp16 hi / lo pairs of `pca_project_from_pairs` (the bits `pca_project(v, ..., pairs, x_bound)` makes of v);
+    the float32 v only when `keep_v`."""
+    _chk(assign_w); _chk(centroids)
+    B, Cc = feat.shape[:2]
+    P = feat.shape[2] * feat.shape[3]
+    K = centroids.shape[0]
+    if not (feat.is_cuda and feat.dtype == torch.float32 and feat.is_contiguous(memory_format=torch.channels_last)):
+        raise _lib.CslamHipError("vlad_aggregate_pairs needs a channels-last float32 device map")
+    a2 = torch.empty((splits, B, K * Cc // splits // 32, 64), dtype=torch.float16, device=feat.device)
+    v = padded_rows(B, K * Cc, feat.device) if keep_v else None
+    _lib.check(_lib.load().cslam_vlad_aggregate_nhwc_pairs_dev(
+        _p(feat), _p(assign_w), _p(assign_b) if assign_b is not None else None, _p(centroids), B, Cc, P, K, float(x_bound),
+        int(splits), _p(a2), _p(v) if keep_v else None, v.stride(0) if keep_v else 0, _stream(a2)))
+    return a2, v
+
+
+def pca_project_from_pairs(a2, components, mean_proj, inv_scale, pairs, x_bound=VLAD_BOUND):
+    """A2 of `vlad_aggregate_pairs` (scaled with the same x_bound) -> normalised [B,Dout]: `pca_project` without its pass over x."""
+    _chk(a2, torch.float16)
+    S, B = a2.shape[:2]
+    din = S * a2.shape[2] * 32
+    if S != pairs[0].shape[0] or din != components.shape[1]:
+        raise _lib.CslamHipError("pair rows and pair weights disagree on the splits or the input width")
+    out = torch.empty((B, components.shape[0]), dtype=torch.float32, device=a2.device)
+    _lib.check(_lib.load().cslam_pca_project_from_pairs_dev(_p(a2), float(x_bound), _p(pairs[0]), float(pairs[1]), S,
+                                                            _p(mean_proj) if mean_proj is not None else None,
+                                                            _p(inv_scale) if inv_scale is not None else None,
+                                                            B, din, components.shape[0], _p(out), _stream(out)))
+    return out
+
+
 def l2_normalize_(x, eps=1e-12, zero_norm_to_one=False):
     """In-place row normalisation of a [n,d] tensor."""
     _chk(x)
@@ -161,7 +208,7 @@ def l2_normalize_(x, eps=1e-12, zero_norm_to_one=False):
 
 def extract_over_lanes(lane_list, frames_u8, chunk, lanes, lane_runner, run_chunk):
     """The batch form of an extractor: `chunk` frames per pass of its pipeline, the passes alternating over `lanes` HIP streams.
-    `lane_list` is the extractor's own list of (stream, runner) pairs, grown here with `lane_runner(i)` (a trunk runner with its
+    `lane_list` is the extractor's own list of (stream, runner) pairs (stream None = the caller's), grown here with `lane_runner(i)` (a trunk runner with its
     own V / M workspaces); `run_chunk(frames, runner)` -> [b, d] runs one pass on the CURRENT stream.  Two passes in flight fill
     each other's tails and launch gaps (NetVLAD: 16.5 -> 15.3 ms per 256 frames with two lanes, no gain from a third, none from
     offsetting the lanes by part of a pass: profiles/r03_v25_two_lanes.log).  The lanes start behind the caller's stream and the
@@ -171,15 +218,22 @@ def extract_over_lanes(lane_list, frames_u8, chunk, lanes, lane_runner, run_chun
     B = int(frames_u8.shape[0])
     starts = list(range(0, B, chunk))
     lanes = min(lanes, len(starts))
+    # Lane 0 is the caller's own stream (None in the list), the others are side streams: `lanes` passes then occupy `lanes`
+    # streams, not `lanes` + 1.  A process has four hardware queues by default and streams share them in turn, so four side lanes
+    # beside the caller's stream put two lanes on one queue, where the second pass started only when the first had finished and then
+    # ran alone on the chip (profiles/r12_step_edges_parent.txt).
     while len(lane_list) < lanes:
-        lane_list.append((torch.cuda.Stream(device=frames_u8.device), lane_runner(len(lane_list))))
+        lane_list.append((torch.cuda.Stream(device=frames_u8.device) if lane_list else None, lane_runner(len(lane_list))))
     cur = torch.cuda.current_stream(frames_u8.device)
+    side = [st for st, _ in lane_list[:lanes] if st is not None]
     out = None
-    for st, _ in lane_list[:lanes]:
+    for st in side:
         st.wait_stream(cur)
     for i, s in enumerate(starts):
-        st, runner = lane_list[i % lanes]
-        with torch.cuda.stream(st):
+        # the caller's stream takes the LAST pass of every round: the shared result below is then allocated on it before any pass
+        # has been queued on it
+        st, runner = lane_list[(i + 1) % lanes]
+        with torch.cuda.stream(cur if st is None else st):
             d = run_chunk(frames_u8[s:s + chunk], runner)
             if out is None:
                 # The shared result lives on the CALLER's stream: allocated inside a lane's context the caching allocator would
@@ -189,10 +243,10 @@ def extract_over_lanes(lane_list, frames_u8, chunk, lanes, lane_runner, run_chun
                 # recorded, so it is not handed out again before the lanes are done with it.
                 with torch.cuda.stream(cur):
                     out = torch.empty((B, d.shape[1]), dtype=d.dtype, device=d.device)
-                for ls, _ in lane_list[:lanes]:
+                for ls in side:
                     out.record_stream(ls)
             out[s:s + d.shape[0]].copy_(d)
-    for st, _ in lane_list[:lanes]:
+    for st in side:
         cur.wait_stream(st)
     return out
 

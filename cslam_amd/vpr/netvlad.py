@@ -226,9 +226,15 @@ class NetVLAD(object):
                 f = self.trunk(x)
         else:
             f = self.encoder(x)
-        v = self.pool(f)
         # the VLAD vector is L2-normalised (netvlad.py:130): |v| <= 1 (one ulp of slack) spares the projection its max-pass
-        return heads.pca_project(v, self.pca_components, self.pca_mean_proj, self.pca_inv_scale, self.pca_pairs, 1.0 + 2.0 ** -20)
+        if heads.vlad_pairs_fit(f, self.pool.centroids, self.pca_pairs):
+            # batches off the Winograd trunk: the VLAD kernel's store writes the projection's pair rows (the same bits, one pass less)
+            a2, _ = heads.vlad_aggregate_pairs(f, self.pool.conv_weight, self.pool.conv_bias, self.pool.centroids,
+                                               self.pca_pairs[0].shape[0], heads.VLAD_BOUND)
+            return heads.pca_project_from_pairs(a2, self.pca_components, self.pca_mean_proj, self.pca_inv_scale, self.pca_pairs,
+                                                heads.VLAD_BOUND)
+        v = self.pool(f)
+        return heads.pca_project(v, self.pca_components, self.pca_mean_proj, self.pca_inv_scale, self.pca_pairs, heads.VLAD_BOUND)
 
     def compute_embeddings_batch_device(self, frames_u8, chunk=512, lanes=2):
         """frames [B,H,W,3] uint8 (device) -> descriptors [B, d] float32 (device), `chunk` frames per pass of the pipeline, the

@@ -180,6 +180,14 @@ int cslam_vlad_aggregate_dev(const float *d_feat, const float *d_assign_w, const
 int cslam_vlad_aggregate_nhwc_dev(const float *d_feat, const float *d_assign_w, const float *d_assign_b,
                                   const float *d_centroids, int B, int C, int P, int K,
                                   float *d_out, int64_t ldo, void *stream);
+/* The matrix form of the channels-last layer (C a multiple of 128 up to 512, 32 <= P <= 200, K = 64, any B) whose final store also
+ * writes the row as the fp16 hi / lo pairs that cslam_pca_project_from_pairs_dev multiplies: d_A2 [S][B][K C / S / 32][hi 32 | lo 32]
+ * of s v, s the power of two from x_bound (> 0: a bound of max |v|, 1 for the L2-normalised vector), S a power of two up to K.
+ * d_out [B, K*C] (pitch ldo) or NULL when only the pairs are wanted.  Both outputs equal cslam_vlad_aggregate_nhwc_dev and the
+ * rows cslam_pca_project_pairs_dev derives from it bit for bit. */
+int cslam_vlad_aggregate_nhwc_pairs_dev(const float *d_feat, const float *d_assign_w, const float *d_assign_b,
+                                        const float *d_centroids, int B, int C, int P, int K, float x_bound, int S,
+                                        void *d_A2, float *d_out, int64_t ldo, void *stream);
 /* CosPlace aggregation head, cslam/vpr/cosplace_utils/network.py:23-29 + layers.py:8-36:
  * L2Norm(C) -> GeM(p, eps) -> Flatten -> Linear(W [Dout, C], b [Dout]) -> L2Norm.
  * feat [B, C, P]; out [B, Dout]. */
@@ -207,6 +215,11 @@ int cslam_pca_project_dev(const float *d_x, int64_t ldx, const float *d_comp, in
 int cslam_pca_project_pairs_dev(const float *d_x, int64_t ldx, float x_bound, const void *d_W2, float inv_sw, int S,
                                 const float *d_mean_proj, const float *d_inv_scale, int B, int Din, int Dout,
                                 float *d_out, void *stream);
+/* The same projection of rows that already are pairs (d_A2 as cslam_vlad_aggregate_nhwc_pairs_dev writes it, scaled with the
+ * same x_bound > 0): the products, the split sums and the epilogue of cslam_pca_project_pairs_dev without its pass over x. */
+int cslam_pca_project_from_pairs_dev(const void *d_A2, float x_bound, const void *d_W2, float inv_sw, int S,
+                                     const float *d_mean_proj, const float *d_inv_scale, int B, int Din, int Dout,
+                                     float *d_out, void *stream);
 /* image transform, cslam/vpr/netvlad.py:202-208 / cosplace.py:73-79:
  * CenterCrop(crop) -> Resize(out_hw, PIL bicubic, antialiased, 8-bit intermediate) ->
  * ToTensor (/255, HWC->CHW) -> Normalize(mean, std).

@@ -1,7 +1,8 @@
 """GPU tests of the chained Winograd transform (csrc/wino_chain.hip; -m gpu): between two F(4x4,3x3) layers on the same map
 (VGG-16 conv3_1 -> 3_2 -> 3_3, conv4_x, conv5_x: cslam/vpr/netvlad.py:163-171) the output transform of layer L and the input
 transform of layer L + 1 run as ONE kernel and y_L stays in LDS.  Compared with the two separate kernels (bit for bit where the
-scales agree) and, through the next layer's products, with a float64 evaluation of the two convolutions."""
+scales agree) and, through the next layer's products, with a float64 evaluation of the two convolutions.  The kernel on its own meets a
+float64 transform per element, at every dispatch corner, in tests/test_wino_transforms_gpu.py."""
 import ctypes as C
 
 import pytest

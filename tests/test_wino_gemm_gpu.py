@@ -1,7 +1,8 @@
 """GPU parity tests of this library's split-fp16 Winograd GEMM (csrc/wino_gemm.hip; -m gpu): the 36 per-frequency
 products of the F(4x4,3x3) form of the trunk's wide convolutions (cslam/vpr/netvlad.py:163-171,227), computed on the
 fp16 matrix pipe from exact hi/lo pairs.  Compared with float64 evaluations of the same sums (tolerances stated per
-test) and, at layer / trunk level, with the plain-fp32 forms beside it."""
+test) and, at layer / trunk level, with the plain-fp32 forms beside it.  The input and output transforms around the products meet a
+float64 transform per element in tests/test_wino_transforms_gpu.py."""
 import os
 
 import numpy as np

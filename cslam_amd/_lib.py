@@ -187,15 +187,22 @@ _SIGNATURES = {
     "cslam_ring_schedule_describe": (_i, [_i, _i, _i, _i, C.POINTER(C.c_int32 * 6), _vp, _i64, _vp, _vp, _vp]),
     "cslam_trunk_timing": (_i, [_i]),
     "cslam_trunk_timing_read": (_i, [C.POINTER(C.c_double * 8)]),
+    "cslam_cloud_from_depth_dev": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_cloud_voxel_dev": (_i, [_vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_cloud_keyframes_dev": (_i, [_vp, _i, _vp, _i, _vp, _vp, _vp, _i, C.c_double, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_map_assemble_dev": (_i, [_vp, _i, _vp, _vp, _vp, _i, C.c_double, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_voxel_profile": (_i, [_i]),
     "cslam_voxel_profile_read": (_i, [C.POINTER(C.c_double * 6), C.POINTER(C.c_int32 * 4)]),
+    "cslam_cloud_profile": (_i, [_i]),
+    "cslam_cloud_profile_read": (_i, [C.POINTER(C.c_double * 7), C.POINTER(C.c_int32 * 4)]),
 }
 
 # declared in include/cslam_hip_experimental.h (A/B partners, profiling hooks, peak micro-benchmarks), not in the stable ABI
 EXPERIMENTAL_SYMBOLS = ("cslam_wino4_input_h3_dev", "cslam_wino2_fused64_dev", "cslam_wino2_fused_c64_dev",
                         "cslam_wino4_fused_c64_dev", "cslam_debug_wfh_prof_dev", "cslam_peak_copy_dev", "cslam_peak_mfma_dev",
                         "cslam_debug_last_candidates", "cslam_ring_schedule_describe", "cslam_trunk_timing", "cslam_trunk_timing_read",
-                        "cslam_voxel_profile", "cslam_voxel_profile_read", "cslam_vis_hypotheses_dev")
+                        "cslam_voxel_profile", "cslam_voxel_profile_read", "cslam_vis_hypotheses_dev", "cslam_cloud_profile",
+                        "cslam_cloud_profile_read")
 EXPORTED_SYMBOLS = tuple(n for n in _SIGNATURES if n not in EXPERIMENTAL_SYMBOLS)
 
 

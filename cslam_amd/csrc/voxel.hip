@@ -31,6 +31,7 @@
 // any row does not exist (8 bytes: they select the sort passes), and the offsets when no host copy was given.
 #include "common.h"
 #include "voxel_plan.h"
+#include "voxel_engine.h"
 
 #pragma clang fp contract(off)
 
@@ -365,6 +366,39 @@ __global__ __launch_bounds__(VOXEL_SEG_BLOCK) void vox_segment_kernel(const doub
 }
 
 // ---- host side ---------------------------------------------------------------------------------
+// the engine cloud.hip shares (voxel_engine.h)
+int voxel_engine_compact(const uint8_t *flags, int64_t n, uint32_t *tile_count, uint32_t *total, uint32_t *rank, uint32_t *src,
+                         uint32_t *seg_end, const int64_t *d_offsets, int n_clouds, int64_t *d_out_offsets, hipStream_t st) {
+    const int64_t flag_tiles = ceil_div64(n, VOXEL_FLAG_BLOCK);
+    hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOXEL_SCAN_BLOCK), 0, st, tile_count, flag_tiles, total);
+    hipLaunchKernelGGL(vox_rank_kernel, dim3((unsigned)flag_tiles), dim3(VOXEL_FLAG_BLOCK), 0, st, flags, n, tile_count, rank, src, seg_end);
+    hipLaunchKernelGGL(vox_out_offsets_kernel, dim3((unsigned)ceil_div64((int64_t)n_clouds + 1, 256)), dim3(256), 0, st, d_offsets,
+                       n_clouds, n, rank, total, d_out_offsets);
+    return CSLAM_OK;
+}
+
+int voxel_engine_sort_heads(const VoxelPlan *pl, const int64_t *d_offsets, int n_clouds, int64_t *d_out_offsets,
+                            hipEvent_t after_sort, hipStream_t st, int *cur_out) {
+    const int64_t n = pl->n;
+    int cur = 0;
+    for (int pass = 0; pass < pl->key_passes + pl->cloud_passes; ++pass) {
+        int shift, from_cloud;
+        voxel_pass_digit(pl, pass, &shift, &from_cloud);
+        hipLaunchKernelGGL(vox_hist_kernel, dim3((unsigned)pl->tiles), dim3(VOXEL_SORT_BLOCK), 0, st, pl->keys[cur], pl->idx[cur], pl->cloud_of, n,
+                           shift, from_cloud, pl->hist);
+        hipLaunchKernelGGL(vox_digit_scan_kernel, dim3(256), dim3(VOXEL_SORT_BLOCK), 0, st, pl->hist, pl->tiles, pl->totals);
+        hipLaunchKernelGGL(vox_scatter_kernel, dim3((unsigned)pl->tiles), dim3(VOXEL_SORT_BLOCK), 0, st, pl->keys[cur], pl->idx[cur], pl->cloud_of, n,
+                           shift, from_cloud, pl->hist, pl->totals, pl->keys[cur ^ 1], pl->idx[cur ^ 1]);
+        cur ^= 1;
+    }
+    if (after_sort) (void)hipEventRecord(after_sort, st);
+    hipLaunchKernelGGL(vox_flag_kernel, dim3((unsigned)pl->flag_tiles), dim3(VOXEL_FLAG_BLOCK), 0, st, pl->keys[cur], pl->cloud_of, n,
+                       pl->invalid_shift, pl->flags, pl->tile_count);
+    *cur_out = cur;
+    return voxel_engine_compact(pl->flags, n, pl->tile_count, pl->rows, pl->rank, pl->seg_start, pl->seg_end, d_offsets, n_clouds,
+                                d_out_offsets, st);
+}
+
 static StreamScratch g_voxel_head_scratch, g_voxel_scratch;
 
 // stage times of the last call, for tools/perf_voxel.py (cslam_voxel_profile)
@@ -452,24 +486,7 @@ CSLAM_API int cslam_voxel_downsample_dev(const double *d_points, const int64_t *
                            origin, meta, pl.invalid_shift, pl.keys[0], pl.idx[0], pl.cloud_of);
         vox_mark(prof, 3, st);
         int cur = 0;
-        for (int pass = 0; pass < pl.key_passes + pl.cloud_passes; ++pass) {
-            int shift, from_cloud;
-            voxel_pass_digit(&pl, pass, &shift, &from_cloud);
-            hipLaunchKernelGGL(vox_hist_kernel, dim3((unsigned)pl.tiles), dim3(VOXEL_SORT_BLOCK), 0, st, pl.keys[cur], pl.idx[cur], pl.cloud_of, n,
-                               shift, from_cloud, pl.hist);
-            hipLaunchKernelGGL(vox_digit_scan_kernel, dim3(256), dim3(VOXEL_SORT_BLOCK), 0, st, pl.hist, pl.tiles, pl.totals);
-            hipLaunchKernelGGL(vox_scatter_kernel, dim3((unsigned)pl.tiles), dim3(VOXEL_SORT_BLOCK), 0, st, pl.keys[cur], pl.idx[cur], pl.cloud_of, n,
-                               shift, from_cloud, pl.hist, pl.totals, pl.keys[cur ^ 1], pl.idx[cur ^ 1]);
-            cur ^= 1;
-        }
-        vox_mark(prof, 4, st);
-        hipLaunchKernelGGL(vox_flag_kernel, dim3((unsigned)pl.flag_tiles), dim3(VOXEL_FLAG_BLOCK), 0, st, pl.keys[cur], pl.cloud_of, n,
-                           pl.invalid_shift, pl.flags, pl.tile_count);
-        hipLaunchKernelGGL(vox_scan_kernel, dim3(1), dim3(VOXEL_SCAN_BLOCK), 0, st, pl.tile_count, pl.flag_tiles, pl.rows);
-        hipLaunchKernelGGL(vox_rank_kernel, dim3((unsigned)pl.flag_tiles), dim3(VOXEL_FLAG_BLOCK), 0, st, pl.flags, n, pl.tile_count, pl.rank,
-                           pl.seg_start, pl.seg_end);
-        hipLaunchKernelGGL(vox_out_offsets_kernel, dim3((unsigned)ceil_div64((int64_t)n_clouds + 1, 256)), dim3(256), 0, st, d_offsets,
-                           n_clouds, n, pl.rank, pl.rows, d_out_offsets);
+        if ((rc = voxel_engine_sort_heads(&pl, d_offsets, n_clouds, d_out_offsets, prof ? g_vox_prof.ev[4] : nullptr, st, &cur))) return rc;
         vox_mark(prof, 5, st);
         const int64_t want = ceil_div64(n, VOXEL_SEG_BLOCK / 64);
         const int64_t cap = (int64_t)(cslam_cu_count() > 0 ? cslam_cu_count() : 256) * 8;

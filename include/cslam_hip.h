@@ -1049,6 +1049,65 @@ int cslam_allgather_queries_dev(cslam_comm_t *comm, const void *d_local, int64_t
                                 void *stream);
 int cslam_exchange_lists_dev(cslam_comm_t *comm, const void *d_send, void *d_recv, int64_t bytes_per_rank, void *stream);
 
+/* ---- coloured keyframe clouds and the merged map (csrc/cloud.hip, rules in csrc/cloud.h) -----------------------------
+ * PCL, image_geometry and depth_image_proc were not available to compare against, and PCL's VoxelGrid sorts with an
+ * unstable std::sort, so its float sums have no defined order: parity with PCL is unpinned.  The rule is what is stated
+ * here and restated in tests/cloud_reference.py; the kernels agree with that restatement bit for bit.  No float atomics:
+ * a cloud's bytes are the same alone or in any batch.  Every call below takes host copies of its offsets (and frame
+ * sizes), which are mandatory, and uses the library's own scratch per (device, stream).
+ *
+ * Frames are batched as for cslam_feat_gray_dev: frame c owns the pixels d_offsets[c] .. d_offsets[c+1]-1 (int64,
+ * n_frames + 1 entries from 0), d_hw[c] = (H, W) int32, H * W = its pixel count.  d_image: uint8, `channels` = 3 (B, G, R)
+ * or 1 per pixel for the whole call; d_depth: uint16 millimetres (depth_type 0) or float32 metres (depth_type 1) for the
+ * whole call; d_cam [n_frames, 4] float64 (fx, fy, cx, cy).  Colours are one uint32 per point, r | g << 8 | b << 16.
+ *
+ * cslam_cloud_from_depth_dev -- `create_colored_pointcloud` (src/front_end/visualization_utils.cpp:8-137, unit rules
+ * of include/cslam/front_end/utils/depth_traits.h:50-64), all in float32: cx_f = float(cx), unit = double(float(1) *
+ * float(0.001)) for uint16 and 1 for float32, kx = float(unit / fx); x = ((float(u) - cx_f) * float(d)) * kx, y likewise,
+ * z = float(d) * float(0.001) for uint16 and d for float32.  Valid: d != 0 (uint16), isfinite(d) (float32: 0 and negative
+ * depths are valid here, as in the reference); an invalid pixel gives three NaNs.  d_points [total, 3] float32 and d_rgb
+ * [total] are the organised clouds, row-major pixel order.
+ *
+ * cslam_cloud_voxel_dev -- `visualization_pointcloud_voxel_subsampling` (src/front_end/rgbd_handler.cpp:640-663):
+ * pcl::VoxelGrid's index rule in float32 with the sum order fixed, then pcl::PassThrough on z.  inv = float(1) /
+ * float(leaf); over the rows with three finite coordinates min_b[a] = floor(min[a] * inv), index i[a] = floor(p[a] * inv) -
+ * float(min_b[a]); one output row per occupied voxel in ascending (iz, iy, ix); xyz = the float32 sum of the voxel's points
+ * in input order, one at a time from zero, divided once by float(count); colour = exact integer sums per channel,
+ * truncating division by the count (PCL's float sums give the same below 65 793 points per voxel).  Then the rows with
+ * 0.0f <= z <= float(max_range) are kept, in order.  d_rgb / d_out_rgb / d_counts may be NULL.  d_out [total, 3], d_out_rgb
+ * and d_counts [total] have the capacity of the input; cloud c's rows are d_out_offsets[c] .. d_out_offsets[c+1]-1.
+ * d_status [n_clouds]: 1 for a cloud with a non-finite cell, a cell of magnitude 2^31 or more, or an index of 2^21 or more
+ * on some axis; it gets no rows (PCL prints a warning and returns the input unfiltered).
+ *
+ * cslam_cloud_keyframes_dev -- both chained on the device (`send_visualization_pointcloud`, rgbd_handler.cpp:665-682,
+ * for visualization.voxel_size > 0): the same bytes as the two calls above.
+ *
+ * cslam_map_assemble_dev -- what the reference's visualiser does with the keyframe clouds at the poses of
+ * `optimized_estimates_callback`, merged into one grid.  d_points [total, 3] float32 or float64 (dtype CSLAM_F32 /
+ * CSLAM_F64), keyframe k owns rows d_offsets[k] .. d_offsets[k+1]-1; d_poses [n_keyframes, 16] float64 row-major.
+ * All in float64: pw[r] = ((T[r,0] x + T[r,1] y) + T[r,2] z) + T[r,3]; cell = floor(pw / voxel) with a true division (a
+ * grid anchored at the world origin, not cslam_voxel_downsample_dev's origin rule), index = cell - the map's smallest
+ * cell per axis; rows in ascending (iz, iy, ix); xyz = sequential float64 sums in input order (keyframe order, then row
+ * order) divided once by the count; colours as above; d_counts = input rows per voxel.  Input rows with a non-finite
+ * coordinate do not exist.  d_out_offsets [2] = {0, rows}; d_status [1] as above (the whole map gets no rows).
+ *
+ * CSLAM_E_INVALID, before anything touches HIP: leaf / voxel not finite or <= 0, max_range negative or NaN, a count
+ * outside [1, 65535], a NULL pointer, host offsets that do not start at 0, that decrease, that do not match the frame
+ * sizes, or that hold 2^31 - 2048 points or more.  Each filter call waits on the host once, after the bounds. */
+int cslam_cloud_from_depth_dev(const uint8_t *d_image, int channels, const void *d_depth, int depth_type,
+                               const int64_t *d_offsets, const int32_t *d_hw, const double *d_cam, int n_frames,
+                               float *d_points, uint32_t *d_rgb, const int64_t *h_offsets, const int32_t *h_hw, void *stream);
+int cslam_cloud_voxel_dev(const float *d_points, const uint32_t *d_rgb, const int64_t *d_offsets, int n_clouds, double leaf,
+                          double max_range, float *d_out, uint32_t *d_out_rgb, int32_t *d_counts, int64_t *d_out_offsets,
+                          int32_t *d_status, const int64_t *h_offsets, void *stream);
+int cslam_cloud_keyframes_dev(const uint8_t *d_image, int channels, const void *d_depth, int depth_type,
+                              const int64_t *d_offsets, const int32_t *d_hw, const double *d_cam, int n_frames, double leaf,
+                              double max_range, float *d_out, uint32_t *d_out_rgb, int32_t *d_counts, int64_t *d_out_offsets,
+                              int32_t *d_status, const int64_t *h_offsets, const int32_t *h_hw, void *stream);
+int cslam_map_assemble_dev(const void *d_points, int dtype, const uint32_t *d_rgb, const int64_t *d_offsets, const double *d_poses,
+                           int n_keyframes, double voxel, double *d_out, uint32_t *d_out_rgb, int32_t *d_counts,
+                           int64_t *d_out_offsets, int32_t *d_status, const int64_t *h_offsets, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -67,6 +67,12 @@ int cslam_trunk_timing_read(double out[8]);
 int cslam_voxel_profile(int enable);
 int cslam_voxel_profile_read(double ms[6], int32_t info[4]);
 
+/* The same for cslam_cloud_voxel_dev, cslam_cloud_keyframes_dev and cslam_map_assemble_dev (tools/perf_keyframe_clouds.py):
+ * ms = {projection or transform + bounds + meta, the host wait, keys, radix passes, segment heads + scan + offsets, segment
+ * sums, clip (flags, scan, rank, gather; nothing for the map)}, info as above. */
+int cslam_cloud_profile(int enable);
+int cslam_cloud_profile_read(double ms[7], int32_t info[4]);
+
 /* The candidate lists stage 1 of the last MFMA-mode search of `bank` left in its workspace (valid until the bank's next
  * search): keys [nq][*nseg][16] float32 in units of q.b / ||b|| (sorted per segment, -inf = empty), rows [nq][*nseg][16]
  * (-1 = empty), and the bound on |key - exact| / ||q|| handed to the float64 certificate.  tests/test_nns_gpu.py checks the

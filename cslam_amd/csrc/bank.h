@@ -62,6 +62,9 @@ struct cslam_bank {
     hipEvent_t ev_flag;
     // diagnostics: where the last MFMA-mode search left its stage-1 candidate lists (cslam_debug_last_candidates)
     const float *dbg_part_key; const int *dbg_part_idx; int dbg_nseg, dbg_nq; double dbg_err_bound;
+    // ... its drop bounds and the form that wrote them (cslam_debug_last_candidate_bounds): tile edge, tiles per segment, and
+    // the key (n_xcd, wpx) of the persistent stage's schedule
+    const float *dbg_part_bound; int dbg_tile, dbg_tps, dbg_ring_key[2];
 };
 
 int bank_ws_reserve(cslam_bank *b, int slot, size_t bytes);

@@ -123,6 +123,7 @@ CSLAM_API int cslam_bank_create(int device, int dim, int64_t capacity_hint, csla
     b->last_nprod = 1; b->f32_backoff = 0; b->f32_backoff_len = 8; b->stage_pinned = false;
     b->pend.active = false; b->pend.deferred = false; b->ev_flag = nullptr;
     b->dbg_part_key = nullptr; b->dbg_part_idx = nullptr; b->dbg_nseg = 0; b->dbg_nq = 0; b->dbg_err_bound = 0.0;
+    b->dbg_part_bound = nullptr; b->dbg_tile = 0; b->dbg_tps = 0; b->dbg_ring_key[0] = 0; b->dbg_ring_key[1] = 0;
     for (int s = 0; s < 4; ++s) { b->stats[s] = 0; b->item_map_key[s] = -1; }
     b->num_cu = 0;
     b->ring_sched.nqt = -1; b->ring_sched.n_rows = -1; b->ring_sched.n_xcd = 0; b->ring_sched.wpx = 0; b->dbg_ring = false;

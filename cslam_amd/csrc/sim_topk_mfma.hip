@@ -811,6 +811,8 @@ int mfma_search_enqueue(cslam_bank *b, const void *d_q, int q_dtype, int64_t ldq
     b->pending_dbg = dbg;
     b->dbg_part_key = part_key; b->dbg_part_idx = part_idx; b->dbg_nseg = nseg; b->dbg_nq = (int)nq; b->dbg_err_bound = err_bound;
     b->dbg_ring = ring;
+    b->dbg_part_bound = part_bound; b->dbg_tile = tile; b->dbg_tps = ring ? 0 : tps;
+    b->dbg_ring_key[0] = ring ? rs->n_xcd : 0; b->dbg_ring_key[1] = ring ? rs->wpx : 0;
     return CSLAM_OK;
 }
 
@@ -874,6 +876,33 @@ CSLAM_API int cslam_debug_last_candidates(cslam_bank_t *b, int64_t nq, int *nseg
     const size_t cnt = (size_t)nq * b->dbg_nseg * KP;
     if (keys) HIP_TRY(hipMemcpy(keys, b->dbg_part_key, cnt * 4, hipMemcpyDeviceToHost));
     if (rows) HIP_TRY(hipMemcpy(rows, b->dbg_part_idx, cnt * 4, hipMemcpyDeviceToHost));
+    return CSLAM_OK;
+}
+
+/* diagnostics: the drop bounds that go with those lists -- bounds [nq][nseg] (float32, key units; -inf = nothing dropped, and
+ * for the lists a query tile of the persistent stage does not have) -- and the form that wrote them:
+ * info = {nseg, tile, fp16 products (0: the f32-input stage), persistent, tiles per segment, n_xcd, wpx, 0}. */
+CSLAM_API int cslam_debug_last_candidate_bounds(cslam_bank_t *b, int64_t nq, int32_t info[8], float *bounds) {
+    ARG_CHECK(b && info, "NULL argument");
+    ARG_CHECK(b->dbg_part_bound && nq >= 0 && nq <= b->dbg_nq, "no MFMA-mode search to report, or nq larger than its batch");
+    BANK_DEVICE(b);
+    info[0] = b->dbg_nseg; info[1] = b->dbg_tile; info[2] = b->last_nprod; info[3] = b->dbg_ring ? 1 : 0;
+    info[4] = b->dbg_tps; info[5] = b->dbg_ring_key[0]; info[6] = b->dbg_ring_key[1]; info[7] = 0;
+    if (!bounds) return CSLAM_OK;
+    HIP_TRY(hipStreamSynchronize(b->last_stream));
+    if (b->dbg_ring) {
+        const RingSchedule &rs = b->ring_sched;
+        const int T = 256, ns_out = b->dbg_nseg;
+        std::vector<float> hb((size_t)rs.total_lists * T);
+        HIP_TRY(hipMemcpy(hb.data(), b->dbg_part_bound, hb.size() * 4, hipMemcpyDeviceToHost));
+        for (int64_t j = 0; j < nq; ++j) {
+            const int qt = (int)(j / T), ns = rs.qt_nseg[qt];
+            const size_t l0 = (size_t)rs.qt_segoff[qt] * T + (size_t)(j - (int64_t)qt * T) * ns;
+            for (int l = 0; l < ns_out; ++l) bounds[(size_t)j * ns_out + l] = l < ns ? hb[l0 + l] : -INFINITY;
+        }
+        return CSLAM_OK;
+    }
+    HIP_TRY(hipMemcpy(bounds, b->dbg_part_bound, (size_t)nq * b->dbg_nseg * 4, hipMemcpyDeviceToHost));
     return CSLAM_OK;
 }
 

@@ -78,6 +78,14 @@ int cslam_cloud_profile_read(double ms[7], int32_t info[4]);
  * (-1 = empty), and the bound on |key - exact| / ||q|| handed to the float64 certificate.  tests/test_nns_gpu.py checks the
  * measured error of the fp16-pair stage against that bound. */
 int cslam_debug_last_candidates(cslam_bank_t *bank, int64_t nq, int *nseg, float *keys, int *rows, double *err_bound);
+/* The drop bounds that go with those lists (valid until the bank's next search): bounds [nq][nseg] float32 in the lists' key
+ * units (NULL: skipped) -- the stage's contract is that every row of list l's bank segment that query j may see and that is
+ * NOT in the list has a key at or below bounds[j][l]; -inf = nothing was dropped, and the lists a query tile of the persistent
+ * stage does not have -- and the form that wrote them: info = {nseg, tile edge (128 | 256), fp16 products (0 = the f32-input
+ * stage, 1 = hi halves, 3 = pairs), persistent (0 | 1), bank tiles per segment (list s = rows [s tps tile, (s + 1) tps tile);
+ * 0 when persistent), n_xcd, wpx (persistent: the arguments of cslam_ring_schedule_describe that give its segments), 0}.
+ * tests/test_nns_stage1_gpu.py checks lists and bounds against float64. */
+int cslam_debug_last_candidate_bounds(cslam_bank_t *bank, int64_t nq, int32_t info[8], float *bounds);
 
 /* The static schedule of the persistent candidate stage (csrc/sim_topk_ring.hip; the matcher's D.D^T of cslam/nns_matching.py:55-61
  * on 256 x 256 tiles) for `nqt` query tiles x `n_rows` bank rows on n_xcd XCDs of wpx workgroups.  Host code only (no GPU needed).

@@ -58,6 +58,32 @@ def assert_topk_equal(idx, sims, cnt, ridx, rsims, rcnt, score_tol):
         assert np.all(both_nan | (np.abs(a - b) <= score_tol)), float(np.nanmax(np.abs(a - b)))
 
 
+# ---- what the candidate stage of the last MFMA-mode search of a NearestNeighborsMatching left behind (diagnostics) ----
+def stage1_candidates(nn, nq):
+    """keys [nq, nseg, 16] float32, rows [nq, nseg, 16] int32, and the error bound handed to the certificate."""
+    import ctypes as C
+    from cslam_amd import _lib
+    nseg, eb = C.c_int(0), C.c_double(0.0)
+    lib = nn._lib
+    _lib.check(lib.cslam_debug_last_candidates(nn._bank, nq, C.byref(nseg), None, None, C.byref(eb)))
+    keys = np.empty((nq, nseg.value, 16), dtype=np.float32)
+    rows = np.empty((nq, nseg.value, 16), dtype=np.int32)
+    _lib.check(lib.cslam_debug_last_candidates(nn._bank, nq, C.byref(nseg), keys.ctypes.data_as(C.c_void_p),
+                                               rows.ctypes.data_as(C.c_void_p), C.byref(eb)))
+    return keys, rows, eb.value
+
+
+def stage1_bounds(nn, nq):
+    """drop bounds [nq, nseg] float32 and info = [nseg, tile, fp16 products, persistent, tiles per segment, n_xcd, wpx, 0]."""
+    import ctypes as C
+    from cslam_amd import _lib
+    info = (C.c_int32 * 8)()
+    _lib.check(nn._lib.cslam_debug_last_candidate_bounds(nn._bank, nq, C.byref(info), None))
+    bounds = np.empty((nq, int(info[0])), dtype=np.float32)
+    _lib.check(nn._lib.cslam_debug_last_candidate_bounds(nn._bank, nq, C.byref(info), bounds.ctypes.data_as(C.c_void_p)))
+    return bounds, [int(v) for v in info]
+
+
 # ---- lidar ScanContext synthetic recipe (heights quantised to 1/256 so fixtures store u16) ----
 def synth_scancontexts(rng, n, rings=20, sectors=60):
     """n random scan contexts [n, rings, sectors] float64: heights in [0, 6), ~30 % empty bins,

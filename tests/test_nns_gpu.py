@@ -10,7 +10,7 @@ import os
 import numpy as np
 import pytest
 
-from helpers import GOLDEN, assert_topk_equal, nns_case_inputs, nns_case_names, unit_rows
+from helpers import GOLDEN, assert_topk_equal, nns_case_inputs, nns_case_names, stage1_candidates, unit_rows
 from oracle import pyoracle
 
 pytestmark = pytest.mark.gpu
@@ -532,19 +532,6 @@ def test_enqueue_finish_halves_equal_the_synchronous_search(nnm):
     assert np.array_equal(r[:, 0], want[0][:, 0])
 
 
-def _stage1_candidates(nnm, nn, nq):
-    import ctypes as C
-    nseg, eb = C.c_int(0), C.c_double(0.0)
-    lib = nn._lib
-    from cslam_amd import _lib
-    _lib.check(lib.cslam_debug_last_candidates(nn._bank, nq, C.byref(nseg), None, None, C.byref(eb)))
-    keys = np.empty((nq, nseg.value, 16), dtype=np.float32)
-    rows = np.empty((nq, nseg.value, 16), dtype=np.int32)
-    _lib.check(lib.cslam_debug_last_candidates(nn._bank, nq, C.byref(nseg), keys.ctypes.data_as(C.c_void_p),
-                                               rows.ctypes.data_as(C.c_void_p), C.byref(eb)))
-    return keys, rows, eb.value
-
-
 @pytest.mark.parametrize("d,f64", [(4096, False), (4096, True), (512, False), (96, True)])
 def test_fp16_pair_candidate_stage_error_is_inside_the_certificates_bound(nnm, monkeypatch, d, f64):
     """The candidate stages on the fp16 matrix pipe (csrc/sim_topk_pair.hip: "h1" = ONE product on the hi halves, the default;
@@ -568,7 +555,7 @@ def test_fp16_pair_candidate_stage_error_is_inside_the_certificates_bound(nnm, m
         monkeypatch.setenv("CSLAM_MFMA_STAGE1", stage)
         idx, sims, cnt = nn.search_batch(q, 5, mode=nnm.MODE_MFMA)
         assert nn.last_stats()[1] == nnm.MODE_MFMA
-        keys, rows, bound = _stage1_candidates(nnm, nn, nq)
+        keys, rows, bound = stage1_candidates(nn, nq)
         out[stage] = (idx, sims, cnt, bound)
         worst = 0.0
         for j in range(nq):
@@ -618,7 +605,7 @@ def test_clustered_near_duplicates_stay_exact_and_back_off_to_the_f32_stage(nnm,
         idx, sims, cnt = nn.search_batch(q, 5, mode=nnm.MODE_MFMA)
         assert nn.last_stats()[1] == nnm.MODE_MFMA
         assert_topk_equal(idx, sims, cnt, oi, os_, oc, 1e-12)
-        _, _, bound = _stage1_candidates(nnm, nn, 4)
+        _, _, bound = stage1_candidates(nn, 4)
         frac[tag] = (nn.last_stats()[0] / 400.0, bound)
         # the stage that ran and the back-off are visible (cslam_bank_last_stage): fp16 stage, then 7 searches left of the first 8
         assert nn.last_stage() == ((1, 8, 16, False) if tag.startswith("h1") else (0, 7, 16, False))
@@ -636,7 +623,7 @@ def test_clustered_near_duplicates_stay_exact_and_back_off_to_the_f32_stage(nnm,
     # an explicit choice of stage is never overridden, and says so
     monkeypatch.setenv("CSLAM_MFMA_STAGE1", "h1")
     idx, sims, cnt = nn.search_batch(q, 5, mode=nnm.MODE_MFMA)
-    assert _stage1_candidates(nnm, nn, 4)[2] > 1e-3
+    assert stage1_candidates(nn, 4)[2] > 1e-3
     assert nn.last_stage()[0] == 1 and nn.last_stage()[3]
     assert_topk_equal(idx, sims, cnt, oi, os_, oc, 1e-12)
 

@@ -1,5 +1,6 @@
 """The front end on the GPU: what a visual keyframe carries, from the image (visual_features.py) or from a stereo pair
-(visual_stereo.py), and the geometric verification of loop closures between such keyframes (visual_registration.py)."""
+(visual_stereo.py), the geometric verification of loop closures between such keyframes (visual_registration.py), and the depth image
+and coloured cloud of a stereo keyframe (stereo_depth.py; the RGB-D one is keyframe_clouds.py)."""
 from .visual_features import (back_project, corner_response, describe, extract_features, extract_keyframes, is_new_keyframe,  # noqa: F401
                               select_keypoints, to_gray)
 from .visual_registration import Keyframe, compute_transformation, register_pairs  # noqa: F401

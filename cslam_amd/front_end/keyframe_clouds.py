@@ -17,7 +17,8 @@ image raises ValueError (the reference warns and returns an empty cloud).
 
 A cloud is a `KeyframeCloud`: points float32 [m, 3], colors uint8 [m, 3] (r, g, b), counts int64 [m] (points per voxel).
 
-Out of scope: stereo frames (the reference sends no cloud for them), depth images smaller than the colour image, the
+Stereo frames have no depth image and the reference sends no cloud for them: `stereo_depth.keyframe_clouds_stereo` makes one
+from the rectified pair and hands it to the chain below.  Out of scope: depth images smaller than the colour image, the
 `range_max` substitution for invalid depths (the reference never passes it), ROS message packing.
 
 There is no CPU path: without the library or a GPU the functions raise CslamHipError.
@@ -106,6 +107,14 @@ class _Frames:
         self.t_depth = to_dev(np.concatenate([d.reshape(-1) for d in dps]).view(np.uint8), dev)      # as bytes: uint16 or float32
         self.t_cam = to_dev(cam, dev)
         self.depth_type, self.channels = key
+
+    @classmethod
+    def on_device(cls, b, t_img, t_depth, t_cam, key):
+        """The same of arrays that are on the device already: `b` their `_Batch`, `t_cam` [n, 4]."""
+        f = cls.__new__(cls)
+        f.b, f.t_img, f.t_depth, f.t_cam = b, t_img, t_depth, t_cam
+        f.depth_type, f.channels = key
+        return f
 
     def head(self):
         b = self.b

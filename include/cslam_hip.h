@@ -843,6 +843,40 @@ int cslam_feat_extract_stereo_dev(const uint8_t *d_left, const int64_t *d_left_o
                                   const int64_t *h_right_off, const int64_t *h_off, const int32_t *h_hw, const double *h_cameras,
                                   void *stream);
 
+/* ------------------------------------------------------------------------------------------------
+ * Dense stereo: the rule above at every pixel of a rectified pair, and the keyframe cloud made from it
+ * (csrc/stereo_dense.hip, its tile plan and bookkeeping in csrc/stereo_dense.h, the rule itself csrc/stereo.h's).  The
+ * reference sends no cloud for a stereo frame (stereo_handler.cpp has no depth image to hand to
+ * send_visualization_pointcloud, rgbd_handler.cpp:665-682); this is what gives stereo robots the map of csrc/cloud.hip.
+ * Pinned: a pixel's status, best and float64 disparity are the bits cslam_feat_stereo_dev gives for a keypoint at that
+ * pixel, for every admitted parameter value; tests/stereo_dense_reference.py restates the dense form in numpy (cost slab by
+ * prefix sums, one back search per right pixel, the rival among the four smallest keys) and agrees bit for bit.  Unpinned:
+ * parity with rtabmap's or OpenCV's dense matchers (StereoBM / StereoSGBM).
+ * Out of scope: unrectified pairs, different principal points, pyramids, speckle and median post-filters.
+ *
+ * cslam_stereo_dense_dev -- d_left, d_right uint8 grey [total pixels] in the ragged layout of the feature section, d_cameras
+ *   float64 [n, 5] (h_cameras required), parameters as cslam_feat_stereo_dev, whose argument checks these are, all before any
+ *   launch ->  d_status uint8 [total]; d_disparity float32 [total] = the float64 disparity rounded once, NaN unless accepted;
+ *   d_depth float32 [total] = (baseline fx) / disparity in float64 rounded once, metres, NaN unless accepted (the float32
+ *   depth of cslam_cloud_keyframes_dev, where a non-finite depth is an invalid pixel); d_best int32 [total, 4] = (d*, a, b, c)
+ *   as cslam_feat_stereo_dev reports it, may be NULL.  No atomics; a frame's bytes are the same alone or in any batch.
+ *   Everything is enqueued on `stream`; scratch is 6 bytes per pixel of the library's own.
+ * cslam_cloud_keyframes_stereo_dev -- what send_visualization_pointcloud would publish for a stereo frame, on one stream with
+ *   the one host wait of cslam_cloud_keyframes_dev: cslam_feat_gray_dev of both sides (d_left / d_right with d_left_off /
+ *   d_right_off as d_src / d_src_off there; every left image has `channels` channels, 1 or 3, the right ones 1 or 3 each),
+ *   cslam_stereo_dense_dev, then cslam_cloud_keyframes_dev on the left image's colours, the float32 depth and the cameras'
+ *   (fx, fy, cx, cy): the same bytes as the staged calls, the same result buffers. */
+int cslam_stereo_dense_dev(const uint8_t *d_left, const uint8_t *d_right, const int64_t *d_off, const int32_t *d_hw, int n,
+                           const double *d_cameras, int min_disparity, int max_disparity, int uniqueness, int lr_tolerance,
+                           float *d_disparity, uint8_t *d_status, float *d_depth, int32_t *d_best, const int64_t *h_off,
+                           const int32_t *h_hw, const double *h_cameras, void *stream);
+int cslam_cloud_keyframes_stereo_dev(const uint8_t *d_left, const int64_t *d_left_off, int channels, const uint8_t *d_right,
+                                     const int64_t *d_right_off, const int64_t *d_off, const int32_t *d_hw, const double *d_cameras,
+                                     int n, int min_disparity, int max_disparity, int uniqueness, int lr_tolerance, double leaf,
+                                     double max_range, float *d_out, uint32_t *d_out_rgb, int32_t *d_counts, int64_t *d_out_offsets,
+                                     int32_t *d_status, const int64_t *h_left_off, const int64_t *h_right_off, const int64_t *h_off,
+                                     const int32_t *h_hw, const double *h_cameras, void *stream);
+
 /* Winograd F(2x2, 3x3) transforms for the 3x3 / stride 1 / pad 1 convolutions of the extractor backbone
  * (the VGG-16 trunk built at cslam/vpr/netvlad.py:163-171; the reference runs it through torch's direct
  * convolution).  Activations are NHWC float32.  conv(x, g) + bias = output(bmm(input(x), U)) with

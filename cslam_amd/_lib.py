@@ -98,7 +98,8 @@ _SIGNATURES = {
     "cslam_pgo_linearize_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_pgo_system_host": (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_pgo_solve_dev": (_i, [C.c_double, _vp, _vp, _vp, _vp]),
-    "cslam_pgo_retract_dev": (_i, [_vp, _vp, _i64, _vp, _vp]),
+    "cslam_pgo_dense_solve_dev": (_i, [_vp, _i64, _vp, _vp, _vp]),
+    "cslam_pgo_retract_dev":(_i, [_vp, _vp, _i64, _vp, _vp]),
     "cslam_pgo_cost_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_pgo_weights_dev": (_i, [_vp, _i64, C.c_double, C.c_double, _vp, _vp, _vp]),
     "cslam_pgo_optimize": (_i, [_i64, _i64, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

@@ -167,6 +167,20 @@ def last_trace():
     return out[:count.value]
 
 
+def dense_solve(S, rhs):
+    """cslam_pgo_dense_solve_dev on float64 device tensors, in place: S [N, N] (its lower triangle becomes the factor) and
+    rhs [N] (becomes the solution).  Returns the status, 1 on a non-positive pivot.  Needs no plan."""
+    lib = _lib.load()
+    _lib.require_gpu()
+    if not (S.is_cuda and rhs.is_cuda and S.is_contiguous() and rhs.is_contiguous() and str(S.dtype) == str(rhs.dtype) == "torch.float64"):
+        raise ValueError("S and rhs must be contiguous float64 device tensors")
+    if S.dim() != 2 or S.shape[0] != S.shape[1] or tuple(rhs.shape) != (S.shape[0],):
+        raise ValueError("S must be N x N and rhs N, not %s and %s" % (tuple(S.shape), tuple(rhs.shape)))
+    status = C.c_int(0)
+    _lib.check(lib.cslam_pgo_dense_solve_dev(S.data_ptr(), S.shape[0], rhs.data_ptr(), C.byref(status), None))
+    return status.value
+
+
 class Staged:
     """The staged entries (cslam_pgo_*_dev) on one graph, device arrays held as torch tensors: what the tests drive kernel
     by kernel, and optimize_staged() below the same loop as cslam_pgo_optimize written in Python."""

@@ -550,16 +550,25 @@ struct PgoWs {
     int device = -1;
     bool planned = false;
     PgoPlan plan;
-    PgoBuf ints, dbl, dense, io;
+    PgoBuf ints, dbl, dense, io, word;            // word: the status of cslam_pgo_dense_solve_dev, which has no plan to keep it in
     // device views into `ints`
     int32_t *ei, *ej, *pa, *pb, *pair_ptr, *pair_fac, *pose_ptr, *pose_fac, *adj_ptr, *adj_nbr, *adj_pair, *jl, *jidx, *seg_ptr, *seg_a,
         *seg_b, *seg_first, *slot_pose, *slot_link, *pose_slot, *slot_seg, *jj_pair, *tgt_r, *tgt_c, *tgt_ptr, *tgt_ent, *status;
     // device views into `dbl`
     double *F, *Hdiag, *g, *Hoff, *E, *Y, *con, *rhs, *delta, *q, *partial, *scalar;
     std::vector<int32_t> trace;                   // accept (1) / reject (0) of every trial step of the last cslam_pgo_optimize
-    void release() { ints.release(); dbl.release(); dense.release(); io.release(); planned = false; device = -1; }
+    void release() { ints.release(); dbl.release(); dense.release(); io.release(); word.release(); planned = false; device = -1; }
 } g_pgo;
 std::mutex g_pgo_mu;
+
+// the workspace lives on the current device: buffers left on another one are freed there first
+int pgo_bind_device() {
+    PgoWs &w = g_pgo;
+    int dev = 0;
+    HIP_TRY(hipGetDevice(&dev));
+    if (w.device != dev) { if (w.device >= 0) { DeviceGuard guard(w.device); w.release(); } w.device = dev; }
+    return CSLAM_OK;
+}
 
 int pgo_set_plan(int64_t n, int64_t nf, const int32_t *h_ei, const int32_t *h_ej, int64_t prior, hipStream_t st) {
     PgoWs &w = g_pgo;
@@ -570,9 +579,8 @@ int pgo_set_plan(int64_t n, int64_t nf, const int32_t *h_ei, const int32_t *h_ej
         return CSLAM_E_LIMIT;
     }
     ARG_CHECK(prc == 0, "cslam_pgo: pose index out of range, an edge with i == j, or a prior outside the poses");
-    int dev = 0;
-    HIP_TRY(hipGetDevice(&dev));
-    if (w.device != dev) { if (w.device >= 0) { DeviceGuard guard(w.device); w.release(); } w.device = dev; }
+    int rc = pgo_bind_device();
+    if (rc) return rc;
     const PgoPlan &p = w.plan;
     const int64_t J = p.J(), S = p.S(), M = p.M(), P = p.P(), N = 6 * J;
     std::vector<int32_t> slot_seg(M);
@@ -592,7 +600,7 @@ int pgo_set_plan(int64_t n, int64_t nf, const int32_t *h_ei, const int32_t *h_ej
     Carver isize;
     ints_layout(isize);
     std::vector<char> stage(isize.at, 0);
-    int rc = w.ints.ensure(isize.at);
+    rc = w.ints.ensure(isize.at);
     if (rc) return rc;
     Carver iplace(w.ints.p);
     ints_layout(iplace);
@@ -647,6 +655,23 @@ int pgo_sum(const double *d_x, const double *d_w, int64_t count, double *h_out, 
     return CSLAM_OK;
 }
 
+// S x = rhs by the panelled factor and the two triangular solves, launches only: the lower triangle of Sd becomes the factor, rhs the
+// solution, *d_status PGO_STATUS_PIVOT on a non-positive pivot (the caller zeroes it).  The one statement of this sequence: pgo_solve
+// and cslam_pgo_dense_solve_dev both run it.
+void pgo_dense_solve(double *Sd, int64_t N, double *d_rhs, int *d_status, hipStream_t st) {
+    for (int64_t k0 = 0; k0 < N; k0 += PGO_CHOL_NB) {
+        const int nb = (int)std::min<int64_t>(PGO_CHOL_NB, N - k0);
+        const int64_t below = N - k0 - nb;
+        hipLaunchKernelGGL(pgo_chol_diag_kernel, dim3(1), dim3(256), 0, st, Sd, N, k0, d_status);
+        if (below > 0) {
+            hipLaunchKernelGGL(pgo_chol_rows_kernel, dim3(pgo_grid(below, 256)), dim3(256), 0, st, Sd, N, k0, nb);
+            const unsigned tiles = (unsigned)ceil_div64(below, PGO_CHOL_NB);
+            hipLaunchKernelGGL(pgo_chol_update_kernel, dim3(tiles, tiles), dim3(256), 0, st, Sd, N, k0, nb);
+        }
+    }
+    hipLaunchKernelGGL(pgo_trisolve_kernel, dim3(1), dim3(256), 0, st, Sd, N, d_rhs);
+}
+
 // (H + lambda I) delta = -g on the system of the last pgo_linearize; *h_predicted = -(g . delta + 1/2 delta . H delta)
 int pgo_solve(double lambda, double *d_delta, int *h_status, double *h_predicted, hipStream_t st) {
     PgoWs &w = g_pgo;
@@ -663,17 +688,7 @@ int pgo_solve(double lambda, double *d_delta, int *h_status, double *h_predicted
     if (nT)
         hipLaunchKernelGGL(pgo_junction_add_kernel, dim3(pgo_grid(nT * 42, 256)), dim3(256), 0, st, nT, J, w.tgt_r, w.tgt_c, w.tgt_ptr, w.tgt_ent,
                            w.con, Sd, w.rhs);
-    for (int64_t k0 = 0; k0 < N; k0 += PGO_CHOL_NB) {
-        const int nb = (int)std::min<int64_t>(PGO_CHOL_NB, N - k0);
-        const int64_t below = N - k0 - nb;
-        hipLaunchKernelGGL(pgo_chol_diag_kernel, dim3(1), dim3(256), 0, st, Sd, N, k0, w.status);
-        if (below > 0) {
-            hipLaunchKernelGGL(pgo_chol_rows_kernel, dim3(pgo_grid(below, 256)), dim3(256), 0, st, Sd, N, k0, nb);
-            const unsigned tiles = (unsigned)ceil_div64(below, PGO_CHOL_NB);
-            hipLaunchKernelGGL(pgo_chol_update_kernel, dim3(tiles, tiles), dim3(256), 0, st, Sd, N, k0, nb);
-        }
-    }
-    hipLaunchKernelGGL(pgo_trisolve_kernel, dim3(1), dim3(256), 0, st, Sd, N, w.rhs);
+    pgo_dense_solve(Sd, N, w.rhs, w.status, st);
     hipLaunchKernelGGL(pgo_backsub_kernel, dim3(pgo_grid(p.n * 6, 256)), dim3(256), 0, st, p.n, w.jidx, w.pose_slot, w.slot_seg, w.seg_a, w.seg_b,
                        w.Y, w.rhs, d_delta);
     hipLaunchKernelGGL(pgo_model_kernel, dim3(pgo_grid(p.n, 256)), dim3(256), 0, st, p.n, w.adj_ptr, w.adj_nbr, w.adj_pair, w.Hdiag, w.Hoff, w.g,
@@ -804,6 +819,24 @@ CSLAM_API int cslam_pgo_solve_dev(double lambda, double *d_delta, int *h_status,
     std::lock_guard<std::mutex> lock(g_pgo_mu);
     PGO_NEED_PLAN();
     return pgo_solve(lambda, d_delta, h_status, h_predicted, (hipStream_t)stream);
+}
+
+CSLAM_API int cslam_pgo_dense_solve_dev(double *d_S, int64_t N, double *d_rhs, int *h_status, void *stream) {
+    ARG_CHECK(d_S && d_rhs && h_status, "cslam_pgo_dense_solve_dev: NULL argument");
+    ARG_CHECK(N >= 1 && N <= 6 * (int64_t)PGO_MAX_JUNCTIONS, "cslam_pgo_dense_solve_dev: N must be in [1, 6 x the junction cap]");
+    std::lock_guard<std::mutex> lock(g_pgo_mu);
+    hipStream_t st = (hipStream_t)stream;
+    int rc = pgo_bind_device();
+    if (rc) return rc;
+    rc = g_pgo.word.ensure(4);
+    if (rc) return rc;
+    int *d_status = (int *)g_pgo.word.p;
+    HIP_TRY(hipMemsetAsync(d_status, 0, 4, st));
+    pgo_dense_solve(d_S, N, d_rhs, d_status, st);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(h_status, d_status, 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    return CSLAM_OK;
 }
 
 CSLAM_API int cslam_pgo_retract_dev(const double *d_poses, const double *d_delta, int64_t n, double *d_out, void *stream) {

@@ -360,6 +360,12 @@ int cslam_pgo_system_host(double *h_Hdiag, double *h_g, double *h_Hoff, int32_t 
  * d_delta [n][6]; *h_status 0, or 1 on a non-positive pivot (nothing aborts; delta is then meaningless);
  * *h_predicted = -(g . delta + 1/2 delta . H delta), the decrease the quadratic model predicts. */
 int cslam_pgo_solve_dev(double lambda, double *d_delta, int *h_status, double *h_predicted, void *stream);
+/* The dense stage of cslam_pgo_solve_dev on its own (the same launch sequence, written once in csrc/pgo.hip): S x = b by the
+ * panelled Cholesky factor and two triangular solves.  d_S [N][N] row-major: the lower triangle with the diagonal is read and
+ * holds the factor on exit; the strict upper triangle never enters a result and is never written.  d_rhs [N]: b in, x out.
+ * *h_status 0, or 1 on a non-positive pivot (the columns before it are still the factor's).  Any N in [1, 6 x the junction
+ * cap], CSLAM_E_INVALID otherwise or on a NULL pointer, before any launch.  Needs no plan. */
+int cslam_pgo_dense_solve_dev(double *d_S, int64_t N, double *d_rhs, int *h_status, void *stream);
 /* Pose3::retract with the full exponential: out_v = T_v Exp(delta_v).  Needs no plan. */
 int cslam_pgo_retract_dev(const double *d_poses, const double *d_delta, int64_t n, double *d_out, void *stream);
 /* NonlinearFactorGraph::error of the weighted graph: E_k to d_E, *h_cost = sum w_k E_k (block partials in block order). */

@@ -346,6 +346,41 @@ def planted_scene(seed, robots=2, length=30, n_true=6, n_out=2, intra=((0, 28), 
     return s
 
 
+def path_edges(walk, reverse):
+    """The edges of a walk; reversed: listed from its far end, every edge (v, u) for (u, v)."""
+    ed = list(zip(walk[:-1], walk[1:]))
+    return [(v, u) for u, v in ed[::-1]] if reverse else ed
+
+
+def subdivided_complete(k):
+    """K_k whose edge (a, b), a < b, carries (a + b) mod 3 interior poses (numbered from k on); where a + b is odd the path is
+    listed from b to a.  For k = 9: 12 direct pairs, 24 segments, 45 poses."""
+    ed, nxt = [], k
+    for a in range(k):
+        for b in range(a + 1, k):
+            m = (a + b) % 3
+            ed += path_edges([a] + list(range(nxt, nxt + m)) + [b], (a + b) % 2 == 1)
+            nxt += m
+    return ed
+
+
+def integer_system(N, seed, density=1.0):
+    """L, A = L L^T, x, b = A x, all int64.  L is lower triangular with off-diagonal entries from {-2 .. 2} (kept with
+    probability `density`, zero otherwise) and a diagonal from {1, 2, 3, 4}; x is from {-3 .. 3}.  Every Schur complement
+    A - L[:, :k] L[:, :k]^T = L[:, k:] L[:, k:]^T and every partial sum of it, in any order, is an integer below
+    4 N max|L|^2 < 2^53; the pivots are perfect squares, the divisions leave integers: a float64 Cholesky factor and both
+    triangular solves are exact whatever their summation order and whether or not products are fused."""
+    rng = np.random.default_rng(seed)
+    L = np.tril(rng.integers(-2, 3, (N, N)), -1)
+    if density < 1.0:
+        L *= rng.random((N, N)) < density
+    L[np.arange(N), np.arange(N)] = rng.integers(1, 5, N)
+    L = L.astype(np.int64)
+    x = rng.integers(-3, 4, N).astype(np.int64)
+    A = L @ L.T
+    return L, A, x, A @ x
+
+
 def plan_graphs(seg_max):
     """name -> (n, ei, ej, prior): the structures the plan and the solver are tested on."""
     def chain(a, b):
@@ -364,6 +399,21 @@ def plan_graphs(seg_max):
     out["two-components"] = (11, chain(0, 4) + chain(5, 10) + [(5, 8)], 0)
     out["reversed"] = (6, [(k + 1, k) for k in range(5)] + [(5, 1)], 0)
     out["loop-at-junction"] = (6, [(0, 1), (1, 2), (2, 3), (3, 1), (1, 4), (4, 5)], 0)
+    # the dense factor's panel edges (48 columns = 8 junctions a panel): two exact panels, and a 6-row remainder after them
+    out["complete16"] = (16, [(a, b) for a in range(16) for b in range(a + 1, 16)], 2)
+    out["complete17"] = (17, [(a, b) for a in range(17) for b in range(a + 1, 17)], 2)
+    # 7 x 8 lattice: the four corners have two neighbours and become one-pose segments, 52 junctions, N = 312 > 256 + 48
+    out["grid7x8"] = (56, [(8 * r + c, 8 * r + c + 1) for r in range(7) for c in range(7)]
+                      + [(8 * r + c, 8 * r + c + 8) for r in range(6) for c in range(8)], 8 * 3 + 3)
+    out["subdivided9"] = (45, subdivided_complete(9), 0)
+    # junctions 0 and 1: a direct edge, its reversed duplicate, and paths of 1, 2, 3 and 5 interior poses; the second and the
+    # fourth are listed from 1 to 0
+    bundle, nxt = [(0, 1), (1, 0)], 2
+    for k, m in enumerate((1, 2, 3, 5)):
+        walk = [0] + list(range(nxt, nxt + m)) + [1]
+        nxt += m
+        bundle += path_edges(walk, k % 2 == 1)
+    out["bundle"] = (nxt, bundle, 0)
     return {k: (n, np.array([e[0] for e in ed], dtype=np.int32), np.array([e[1] for e in ed], dtype=np.int32), p)
             for k, (n, ed, p) in out.items()}
 

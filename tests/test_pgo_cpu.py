@@ -325,6 +325,30 @@ def test_plan_structure(planlib, name):
         assert p.n_cut == 2 and sorted(len(x) for x in p.interiors()) == [SEG_MAX, SEG_MAX]
     if name == "two-components":
         assert {0, 4, 8, 10} == set(p.jl.tolist())          # the ring 5-6-7-8 hangs on 8; nothing ties it to the prior
+    kinds = p.tgt_ent & 3
+    lists = np.diff(p.tgt_ptr)
+    if name == "complete16":
+        assert (J, S) == (16, 0) and len(p.jj_pair) == 120                       # N = 96: two exact panels of the dense factor
+    if name == "complete17":
+        assert (J, S) == (17, 0) and len(p.jj_pair) == 136                       # N = 102: a 6-row remainder after them
+    if name == "grid7x8":
+        assert (J, S) == (52, 4) and sorted(p.interiors()) == [[0], [7], [48], [55]]         # N = 312; the corners are segments
+        assert len(p.jj_pair) == 97 - 8                                           # every lattice edge that touches no corner
+    if name == "subdivided9":
+        assert p.n == 45 and (J, S) == (9, 24) and list(p.jl) == list(range(9)) and len(p.jj_pair) == 12
+        # a segment is walked from its lower junction, so between two junctions it enters the block (b, a) as BA whichever way
+        # its edges are listed (AB is the kind of a ring that starts and ends on one junction, as in "ring"); the listing order
+        # reaches the plan as the reversed bit of the pair's factors, and both values occur
+        off = np.concatenate([kinds[p.tgt_ptr[T]:p.tgt_ptr[T + 1]] for T in range(len(p.tgt_r)) if p.tgt_r[T] != p.tgt_c[T]])
+        assert len(off) == 24 and np.all(off == 3), "PGO_KIND_BA"
+        assert set((p.pair_fac & 1).tolist()) == {0, 1} and set((p.slot_link & 1).tolist()) == {0, 1}
+        # a junction is the first end of some segments and the last of others: AA and BB in one diagonal list
+        assert any({0, 1} <= set(kinds[p.tgt_ptr[T]:p.tgt_ptr[T + 1]].tolist()) for T in range(len(p.tgt_r)))
+    if name == "bundle":
+        assert p.n == 13 and (J, S) == (2, 4) and sorted(len(x) for x in p.interiors()) == [1, 2, 3, 5]
+        assert list(zip(p.tgt_r.tolist(), p.tgt_c.tolist())) == [(0, 0), (1, 0), (1, 1)] and list(lists) == [4, 4, 4]
+        assert list(p.jj_pair) == [0] and list(p.pair_fac[p.pair_ptr[0]:p.pair_ptr[1]]) == [0, 3]   # (0, 1) and its reversed twin
+        assert set((p.pair_fac & 1).tolist()) == {0, 1}
 
 
 def test_plan_promotes_one_pose_of_a_cycle_without_junction(planlib):
@@ -457,6 +481,30 @@ def test_plan_lists_carry_the_elimination(planlib, name):
         got = eliminate(p, Hd, g, Hoff, lam).ravel()
         res = lambda x: np.linalg.norm(A @ x + g.ravel()) / np.linalg.norm(g)
         assert res(got) <= 10 * res(want) + 1e-13, (name, lam, res(got), res(want))
+
+
+# ---- the integer systems of the GPU's exact tests ------------------------------------------------------------------------------------
+@pytest.mark.parametrize("N,density", [(1, 1.0), (49, 1.0), (102, 0.1), (354, 1.0), (354, 0.1)])
+def test_integer_systems_are_exact_in_float64(N, density):
+    """The right-looking factor in 48-column panels and the two triangular solves, in float64 with numpy's own summation
+    orders, return L and x of ref.integer_system exactly: what tests/test_pgo_gpu.py then asks of the kernels bit for bit."""
+    from scipy.linalg import solve_triangular
+    L, A, x, b = ref.integer_system(N, 7, density)
+    assert np.array_equal(A, A.T) and np.array_equal(np.triu(L, 1), np.zeros_like(L)) and np.abs(b).max() < 2 ** 31
+    if N > 100:
+        fill = np.count_nonzero(np.tril(L, -1)) / (N * (N - 1) / 2)
+        assert (0.07 < fill < 0.13) if density < 1.0 else (0.75 < fill < 0.85)      # a fifth of {-2 .. 2} is 0
+    S = A.astype(np.float64)
+    for k0 in range(0, N, 48):
+        k1 = min(N, k0 + 48)
+        S[k0:k1, k0:k1] = np.linalg.cholesky(S[k0:k1, k0:k1])
+        if k1 < N:
+            S[k1:, k0:k1] = solve_triangular(S[k0:k1, k0:k1], S[k1:, k0:k1].T, lower=True).T
+            S[k1:, k1:] -= S[k1:, k0:k1] @ S[k1:, k0:k1].T
+    F = np.tril(S)
+    assert np.array_equal(F, L.astype(np.float64))
+    y = solve_triangular(F, b.astype(np.float64), lower=True)
+    assert np.array_equal(solve_triangular(F.T, y, lower=False), x.astype(np.float64))
 
 
 # ---- the restatement as an optimiser -------------------------------------------------------------------------------------------------

@@ -103,19 +103,10 @@ def test_linearize_matches_the_restatement_and_repeats_bit_for_bit():
 
 
 # ---- solve -----------------------------------------------------------------------------------------------------------------------------
-@pytest.mark.parametrize("name", sorted(ref.plan_graphs(SEG_MAX)))
-def test_solve_against_spsolve(name):
-    """|| (H + lam I) d + g || / || g || <= 10 x the same figure of spsolve's solution of the same system (the system the GPU
-    linearised, read back), and || d - d_spsolve || <= || A^-1 || (|| res || + || res_spsolve ||): the two solutions of A x = b
-    differ by A^-1 applied to the difference of their residuals; || A^-1 ||_2 = 1 / lambda_min(A) from a dense eigh."""
-    n, ei, ej, prior = ref.plan_graphs(SEG_MAX)[name]
-    poses, meas, sig = ref.random_graph_values(n, ei, ej, 3)
-    st = pg.Staged(problem(n, ei, ej, meas, sig, prior, poses))
-    assert st.info["longest"] <= SEG_MAX and st.info["seg_max"] == SEG_MAX
-    st.linearize(st.dev(poses), st.dev(np.ones(len(ei) + 1)))
+def check_solve_against_spsolve(st, n, name, lams):
+    """The two bounds of test_solve_against_spsolve on the system `st` has linearised, at every lambda of `lams`."""
     Hd, g, Ho, pa, pb = st.system()
     Hoff = {(int(a), int(b)): Ho[q] for q, (a, b) in enumerate(zip(pa, pb))}
-    lams = [1e-5, 1e5] + ([] if name == "two-components" else [0.0])      # one component has no prior: singular at 0
     for lam in lams:
         A = ref.assemble(n, Hd, Hoff, lam)
         b = -g.ravel()
@@ -124,7 +115,8 @@ def test_solve_against_spsolve(name):
         got = delta.cpu().numpy().ravel().copy()
         assert status == 0
         res = lambda x: np.linalg.norm(A @ x - b)
-        print("%s lam %g: residual %.3g (spsolve %.3g)" % (name, lam, res(got) / np.linalg.norm(b), res(want) / np.linalg.norm(b)))
+        print("%s lam %g: residual %.3g (spsolve %.3g), %.2f x" % (name, lam, res(got) / np.linalg.norm(b), res(want) / np.linalg.norm(b),
+                                                                  res(got) / res(want)))
         assert res(got) <= 10.0 * res(want), (name, lam, res(got), res(want))
         inv_norm = 1.0 / np.linalg.eigvalsh(A.toarray())[0]
         assert np.linalg.norm(got - want) <= inv_norm * (res(got) + res(want)), (name, lam)
@@ -135,6 +127,29 @@ def test_solve_against_spsolve(name):
         assert np.array_equal(delta2.cpu().numpy().ravel(), got) and predicted2 == predicted, "two runs must agree bit for bit"
 
 
+@pytest.mark.parametrize("name", sorted(ref.plan_graphs(SEG_MAX)))
+def test_solve_against_spsolve(name):
+    """|| (H + lam I) d + g || / || g || <= 10 x the same figure of spsolve's solution of the same system (the system the GPU
+    linearised, read back), and || d - d_spsolve || <= || A^-1 || (|| res || + || res_spsolve ||): the two solutions of A x = b
+    differ by A^-1 applied to the difference of their residuals; || A^-1 ||_2 = 1 / lambda_min(A) from a dense eigh."""
+    n, ei, ej, prior = ref.plan_graphs(SEG_MAX)[name]
+    poses, meas, sig = ref.random_graph_values(n, ei, ej, 3)
+    st = pg.Staged(problem(n, ei, ej, meas, sig, prior, poses))
+    assert st.info["longest"] <= SEG_MAX and st.info["seg_max"] == SEG_MAX
+    st.linearize(st.dev(poses), st.dev(np.ones(len(ei) + 1)))
+    check_solve_against_spsolve(st, n, name, [1e-5, 1e5] + ([] if name == "two-components" else [0.0]))   # no prior there: singular at 0
+
+
+def test_solve_against_spsolve_at_mid_size():
+    """4 robots x 120 poses and 40 closures: at least 87 junctions, so a dense system of 522 rows or more, 11 panels, three
+    workgroups in the rows kernel and three strides in the triangular solve, with segments of every length between them."""
+    sc = ref.planted_scene(3, robots=4, length=120, n_true=40, n_out=0)
+    st = pg.Staged(scene_problem(sc))
+    assert sc.graph.n == 480 and st.info["junctions"] >= 87 and st.info["segments"] > 0
+    st.linearize(st.dev(sc.init), st.dev(np.ones(sc.graph.nf + 1)))
+    check_solve_against_spsolve(st, sc.graph.n, "mid-size (%d junctions)" % st.info["junctions"], [1e-5, 1e5])
+
+
 def test_non_positive_pivot_is_a_status():
     """Weights of zero on every factor: H = 0, and at lambda = 0 the first pivot is not positive.  Nothing aborts."""
     n, ei, ej, prior = ref.plan_graphs(SEG_MAX)["adjacent-junctions"]
@@ -143,6 +158,153 @@ def test_non_positive_pivot_is_a_status():
     st.linearize(st.dev(poses), st.dev(np.zeros(len(ei) + 1)))
     assert st.solve(0.0)[1] == 1
     assert st.solve(1.0)[1] == 0
+
+
+# ---- the dense factor on its own: cslam_pgo_dense_solve_dev, the launch sequence pgo_solve runs ------------------------------------------
+NB = 48                                                      # PGO_CHOL_NB
+# one short panel; exactly one; one row over; two exact panels; full panels and remainders of 1, 6 and 24; the last N with one
+# workgroup in the rows kernel (256 rows below the first panel) and the first with two; a 7 x 7 tile grid whose last tile has one row
+DENSE_SIZES = (1, 6, 47, 48, 49, 54, 96, 97, 102, 304, 305, 312, 337, 354)
+DENSE_CASES = [(N, 1.0) for N in DENSE_SIZES] + [(102, 0.1), (354, 0.1)]       # 10 % fill: no neighbour hides a skipped tile
+
+
+def dense_solve(A, b, upper=None):
+    """Lower triangle of S and the solution after the call, the whole S, the status.  `upper` fills the strict upper triangle."""
+    import torch
+    S = np.array(A, dtype=np.float64)
+    if upper is not None:
+        S[np.triu_indices(len(S), 1)] = upper
+    dS, drhs = torch.from_numpy(S).cuda(), torch.from_numpy(np.array(b, dtype=np.float64)).cuda()
+    status = pg.dense_solve(dS, drhs)
+    S = dS.cpu().numpy()
+    return np.tril(S), drhs.cpu().numpy(), S, status
+
+
+def first_difference(got, want, what, cols=None):
+    """'' when the arrays agree; else where they first differ, in the terms of the kernels: panel = column block of 48, and
+    the update tile (ti, tj) that entry has after panel k is (row block - k - 1, column block - k - 1)."""
+    bad = got != want
+    if cols is not None:
+        bad[:, cols:] = False
+    if not bad.any():
+        return ""
+    if got.ndim == 1:
+        r = int(np.flatnonzero(bad)[0])
+        return "%s: %d of %d entries differ, first at row %d (panel %d, row %d in it, stride %d of the triangular solve): got %r, want %r" % (
+            what, bad.sum(), bad.size, r, r // NB, r % NB, r // 256, got[r], want[r])
+    c = int(np.flatnonzero(bad.any(axis=0))[0])                 # columns are finished left to right
+    r = int(np.flatnonzero(bad[:, c])[0])
+    return ("%s: %d entries differ, the leftmost column's first at row %d, column %d: panel %d (column %d in it), row block %d (row %d in "
+            "it; tile (%d, %d) of the update after panel 0; rows kernel workgroup %d); got %r, want %r"
+            % (what, bad.sum(), r, c, c // NB, c % NB, r // NB, r % NB, r // NB - 1, c // NB - 1, max(r - (c // NB + 1) * NB, 0) // 256,
+               got[r, c], want[r, c]))
+
+
+@pytest.mark.parametrize("N,density", DENSE_CASES)
+def test_dense_factor_and_solution_are_exact_on_integer_systems(N, density):
+    """A = L L^T and b = A x in integers (ref.integer_system): every intermediate of the factor and of both solves is an
+    integer below 2^53, so the factor is L and the solution x to the bit, whatever the order of the sums.  No tolerance."""
+    L, A, x, b = ref.integer_system(N, 100 + N, density)
+    F, sol, S, status = dense_solve(A, b)
+    why = first_difference(F, L.astype(np.float64), "factor N = %d (status %d)" % (N, status))
+    assert np.array_equal(F, L.astype(np.float64)), why
+    assert status == 0
+    assert np.array_equal(np.triu(S, 1), np.triu(A.astype(np.float64), 1)), "the strict upper triangle is not written"
+    why = first_difference(sol, x.astype(np.float64), "solution N = %d" % N)
+    assert np.array_equal(sol, x.astype(np.float64)), why
+    F2, sol2, S2, status2 = dense_solve(A, b)
+    assert status2 == 0 and np.array_equal(S2, S) and np.array_equal(sol2, sol), "two runs must agree bit for bit"
+
+
+@pytest.mark.parametrize("N", (49, 354))
+def test_dense_solve_never_touches_the_strict_upper_triangle(N):
+    """NaN (with a payload) above the diagonal on entry: the same bits there on exit, none below it or in the solution."""
+    L, A, x, b = ref.integer_system(N, 200 + N)
+    nan = np.array([0x7ff8dead0000beef], dtype=np.uint64).view(np.float64)[0]
+    F, sol, S, status = dense_solve(A, b, upper=nan)
+    iu = np.triu_indices(N, 1)
+    assert status == 0 and np.all(S[iu].view(np.uint64) == np.uint64(0x7ff8dead0000beef))
+    assert not np.isnan(F).any() and not np.isnan(sol).any()
+    assert np.array_equal(F, L.astype(np.float64)), first_difference(F, L.astype(np.float64), "factor N = %d" % N)
+    assert np.array_equal(sol, x.astype(np.float64)), first_difference(sol, x.astype(np.float64), "solution N = %d" % N)
+
+
+@pytest.mark.parametrize("p", (0, 47, 48, 100, 101))
+def test_dense_zero_pivot_is_a_status_and_leaves_the_columns_before_it(p):
+    """A[p][p] lowered by L[p][p]^2 makes the pivot of column p exactly 0: first column, panel end, panel start, remainder
+    panel, last column of N = 102.  The call returns, the status says so, and columns < p are still L's."""
+    N = 102
+    L, A, x, b = ref.integer_system(N, 300)
+    assert dense_solve(A, b)[3] == 0
+    A = A.copy()
+    A[p, p] -= L[p, p] ** 2
+    F, sol, S, status = dense_solve(A, b)
+    assert status == 1
+    why = first_difference(F, L.astype(np.float64), "columns before the pivot %d" % p, cols=p)
+    assert np.array_equal(F[:, :p], L[:, :p].astype(np.float64)), why
+
+
+def gamma(k):
+    u = np.longdouble(2.0) ** -53
+    return k * u / (1 - k * u)
+
+
+def real_system(N, graded, seed):
+    """A = G G^T / N + I (condition about 5), or D A D with D graded from 1 to 1e-4 (condition about 1e8); b = A x."""
+    rng = np.random.default_rng(seed)
+    G = rng.standard_normal((N, N))
+    A = G @ G.T / N + np.identity(N)
+    A = 0.5 * (A + A.T)
+    if graded:
+        D = 10.0 ** (-4.0 * np.arange(N) / (N - 1))
+        A = A * D[:, None] * D[None, :]
+    return A, A @ rng.uniform(-1.0, 1.0, N)
+
+
+@pytest.mark.parametrize("N,graded", [(102, False), (102, True), (354, False), (354, True)])
+def test_dense_factor_and_solve_meet_the_backward_error_bounds(N, graded):
+    """Higham, Accuracy and Stability of Numerical Algorithms, Theorems 10.3 and 10.4, component-wise, in np.longdouble on the
+    factor L the GPU returned:  |A - L L^T| <= gamma_k |L| |L^T| with k = 2 (N + 1), and |b - A x| <= gamma_k |L| |L^T| |x| with
+    k = 2 (3 N + 1); gamma_k = k u / (1 - k u), u = 2^-53.  They hold for any order of the sums and with fused multiply-adds;
+    the 2 in k allows a square root and a division within one ulp that are not correctly rounded.  Nothing is measured.
+    On one MI355X the worst entry is at 0.037 (factor) and 0.013 (solve) of its bound, both on the graded N = 102."""
+    assert np.finfo(np.longdouble).eps <= 2.0 ** -63, "the bounds are evaluated in 80-bit arithmetic"
+    A, b = real_system(N, graded, 400 + N)
+    cond = np.linalg.cond(A)
+    assert (cond < 10.0) if not graded else (1e7 < cond < 1e9), cond
+    F, sol, S, status = dense_solve(A, b)
+    assert status == 0
+    Al, Fl, xl, bl = (np.asarray(v, dtype=np.longdouble) for v in (A, F, sol, b))
+    env = np.abs(Fl) @ np.abs(Fl.T)
+    fac = np.abs(Al - Fl @ Fl.T) / (gamma(2 * (N + 1)) * env)
+    slv = np.abs(bl - Al @ xl) / (gamma(2 * (3 * N + 1)) * (env @ np.abs(xl)))
+    print("dense N = %d cond %.3g: worst |A - L L^T| at %.4f of its bound, worst |b - A x| at %.4f of its bound"
+          % (N, cond, float(fac.max()), float(slv.max())))
+    r, c = np.unravel_index(int(np.argmax(fac)), fac.shape)
+    assert fac.max() <= 1.0, "row %d, column %d (panel %d, row block %d): %r of the bound" % (r, c, c // NB, r // NB, float(fac.max()))
+    assert slv.max() <= 1.0, "row %d: %r of the bound" % (int(np.argmax(slv)), float(slv.max()))
+
+
+def test_dense_solve_argument_errors_come_before_any_launch():
+    import ctypes as C
+    import torch
+    lib = _lib.load()
+    S, rhs, status = torch.eye(6, dtype=torch.float64, device="cuda"), torch.ones(6, dtype=torch.float64, device="cuda"), C.c_int(7)
+    cap = 6 * 4096
+    for args in ((None, 6, rhs.data_ptr(), C.byref(status)), (S.data_ptr(), 6, None, C.byref(status)), (S.data_ptr(), 6, rhs.data_ptr(), None),
+                 (S.data_ptr(), 0, rhs.data_ptr(), C.byref(status)), (S.data_ptr(), -6, rhs.data_ptr(), C.byref(status)),
+                 (S.data_ptr(), cap + 1, rhs.data_ptr(), C.byref(status))):
+        with pytest.raises(_lib.CslamHipError, match="cslam_pgo_dense_solve_dev"):
+            _lib.check(lib.cslam_pgo_dense_solve_dev(*args, None))
+    torch.cuda.synchronize()
+    assert status.value == 7 and np.array_equal(S.cpu().numpy(), np.identity(6)) and np.array_equal(rhs.cpu().numpy(), np.ones(6))
+    with pytest.raises(ValueError):
+        pg.dense_solve(S, rhs[:5])
+    with pytest.raises(ValueError):
+        pg.dense_solve(S.float(), rhs)
+    with pytest.raises(ValueError):
+        pg.dense_solve(S.t()[:, :3], rhs)
+    assert pg.dense_solve(S, rhs) == 0
 
 
 # ---- retract, cost, weights ------------------------------------------------------------------------------------------------------------

@@ -20,8 +20,8 @@ import collections
 import numpy as np
 
 from .. import _lib
-from ..front_end.keyframe_clouds import pack_colors, result_args, result_buffer, unpack_result
-from ..lidar_pr._batch import gpu, host, offsets, stream, to_dev
+from ..front_end.keyframe_clouds import pack_colors, unpack_result
+from ..lidar_pr._batch import gpu, host, offsets, result_args, result_buffer, stream, to_dev
 from ..lidar_pr.voxel import VoxelSizeError
 from .pose_graph import as_pose
 

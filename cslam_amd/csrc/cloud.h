@@ -1,5 +1,6 @@
-// The arithmetic rules of cloud.hip, once: the back-projection of a depth pixel, the voxel cell of a coordinate in both
-// precisions, the colour packing, and how the call's first scratch block is carved.  Plain C++ without HIP (the kernels
+// The arithmetic rules of cloud.hip, once: the back-projection of a depth pixel, the three grid rules of the voxel filters
+// (PCL's for keyframe clouds, the map's, open3d's for lidar clouds) with the one key packing they share, the colour
+// packing, and how the call's first scratch block is carved.  Plain C++ without HIP (the kernels
 // include it with CLOUD_HD = __host__ __device__), so that the host tests compile the very same functions and a
 // stand-alone program runs them under host sanitizers.  Every float operation is written once and nothing is contracted.
 #pragma once
@@ -96,11 +97,12 @@ template <typename S> CLOUD_HD static inline uint32_t cloud_index(S p, S scale, 
 }
 
 // x << s for 0 <= s < 64, from 32-bit shifts only: v_lshlrev_b32 and v_lshrrev_b32, wherever the allocator puts the amount.
-// Written as a 64-bit shift by a per-lane amount, cloud_key_kernel<float> compiles to `v_lshlrev_b64 v[6:7], v15, v[10:11]`
-// in a wave of 16 VGPRs.  For gfx90a the same compiler wraps exactly that instruction in `v_swap_b32 v0, v15` (its guard
-// for a 64-bit shift whose amount sits in the last register of an 8-register block); for gfx950 it emits it bare, and on
-// an MI355X some waves then packed iy with a shift of 0 (tools/probe_shift64.hip shows the instruction alone).
-// vox_key_kernel shifts by v20 / v21 of 36 and is not touched by this.
+// Written as a 64-bit shift by a per-lane amount, a key kernel of 16 VGPRs compiled to `v_lshlrev_b64 v[6:7], v15, v[10:11]`.
+// For gfx90a the same compiler wraps exactly that instruction in `v_swap_b32 v0, v15` (its guard for a 64-bit shift whose
+// amount sits in the last register of an 8-register block); for gfx950 it emits it bare, and on an MI355X some waves then
+// packed iy with a shift of 0 (tools/probe_shift64.hip shows the instruction alone).  Which register holds the amount is
+// the allocator's choice, so EVERY key of every rule is packed by this function: no key kernel shifts 64 bits by a
+// per-lane amount.
 CLOUD_HD static inline uint64_t cloud_shift(uint32_t x, int s) {
     const uint32_t lo = s < 32 ? x << s : 0u;
     const uint32_t hi = s == 0 ? 0u : (s < 32 ? x >> (32 - s) : x << (s - 32));
@@ -111,6 +113,56 @@ CLOUD_HD static inline uint64_t cloud_shift(uint32_t x, int s) {
 CLOUD_HD static inline uint64_t cloud_key(uint32_t ix, uint32_t iy, uint32_t iz, int shift_y, int shift_z) {
     return cloud_shift(iz, shift_z) | cloud_shift(iy, shift_y) | ix;
 }
+
+// ---- the three grid rules, as the kernels take them ---------------------------------------------------------------
+// A rule names its scalar S and its parameter P, the most significant axis of its key (MAJOR: the shift of that axis is
+// meta[0] = bits[1] + bits[2 - MAJOR], the shift of y is meta[1] = bits[2 - MAJOR]), and
+//   range(lo, hi, param, base, bits): what the bounds of a cloud give, returning the cloud's status
+//   index(p, param, base)           : the index of a coordinate, below 2^21 for every finite row of a cloud with status 0
+//   key(ix, iy, iz, shift_major, shift_y)
+template <typename T> struct GridCells {                   // cloud_cell above in either precision: base = the cell of the minimum
+    typedef T S;
+    typedef T P;
+    static constexpr int MAJOR = 2;
+    CLOUD_HD static inline int range(const T lo[3], const T hi[3], T scale, T base[3], int bits[3]) {
+        return cloud_axis_range(lo, hi, scale, base, bits);
+    }
+    CLOUD_HD static inline uint32_t index(T p, T scale, T base) { return cloud_index(p, scale, base); }
+    CLOUD_HD static inline uint64_t key(uint32_t ix, uint32_t iy, uint32_t iz, int shift_major, int shift_y) {
+        return cloud_key(ix, iy, iz, shift_y, shift_major);
+    }
+};
+typedef GridCells<float> GridPcl;                          // keyframe filter: floorf(p * inv), param = inv = 1.0f / leaf
+typedef GridCells<double> GridMap;                         // swarm map: floor(p / voxel), param = voxel
+
+// Lidar down-sampling, open3d's voxel_down_sample: base = origin = min - voxel / 2 (the half is computed on the host),
+// index = floor((p - origin) / voxel) with a true division, x most significant.  The index of the maximum is the largest
+// index (every step is monotone); status 1 when it is not in [0, 2^21), which includes a NaN or infinite quotient.
+struct GridOpen3dParam { double voxel, half; };
+struct GridOpen3d {
+    typedef double S;
+    typedef GridOpen3dParam P;
+    static constexpr int MAJOR = 0;
+    CLOUD_HD static inline double cell(double p, double voxel, double origin) { return floor((p - origin) / voxel); }
+    CLOUD_HD static inline int range(const double lo[3], const double hi[3], P g, double base[3], int bits[3]) {
+        int over = 0;
+        for (int a = 0; a < 3; ++a) {
+            base[a] = lo[a] - g.half;
+            bits[a] = 0;
+            const double q = cell(hi[a], g.voxel, base[a]);
+            if (!(q >= 0.0 && q < (double)(1 << VOXEL_AXIS_BITS))) {
+                over = 1;
+                continue;
+            }
+            for (uint32_t w = (uint32_t)q; w; w >>= 1) ++bits[a];
+        }
+        return over;
+    }
+    CLOUD_HD static inline uint32_t index(double p, P g, double base) { return (uint32_t)(int32_t)cell(p, g.voxel, base); }
+    CLOUD_HD static inline uint64_t key(uint32_t ix, uint32_t iy, uint32_t iz, int shift_major, int shift_y) {
+        return cloud_key(iz, iy, ix, shift_y, shift_major);      // the same packing with x and z exchanged
+    }
+};
 
 // clip of the keyframe filter's rows: PassThrough on z with limits [0, max_range], both ends kept
 CLOUD_HD static inline bool cloud_clip_keep(float z, float max_range) { return 0.0f <= z && z <= max_range; }

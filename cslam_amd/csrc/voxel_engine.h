@@ -1,6 +1,7 @@
-// The part of the voxel engine (voxel.hip) that does not depend on how a key was made: the stable radix sort of
-// (key, point index), the segment heads, their scan and the output offsets.  voxel.hip and cloud.hip both call it on a
-// placed VoxelPlan whose keys[0], idx[0] and cloud_of a key kernel has filled.  Hidden visibility: not part of the C ABI.
+// The voxel engine (voxel.hip), which does not depend on how a key was made: the stable radix sort of (key, point index),
+// the segment heads, their scan and the output offsets.  The one filter chain of cloud.hip calls it, for all three grid
+// rules, on a placed VoxelPlan whose keys[0], idx[0] and cloud_of the key kernel has filled.  Hidden visibility: not part
+// of the C ABI.
 #pragma once
 #include <hip/hip_runtime.h>
 #include "voxel_plan.h"

@@ -1,4 +1,5 @@
-// Host-side planning of cslam_voxel_downsample_dev (voxel.hip): which radix passes run and how the scratch is carved.
+// Host-side planning of a voxel filter call (the chain of cloud.hip on the engine of voxel.hip): which radix passes run
+// and how the scratch is carved.
 // Plain C++ without HIP, so that it can also be compiled into a stand-alone program and run under host sanitizers.
 #pragma once
 #include <stdint.h>

@@ -28,8 +28,9 @@ import collections
 import numpy as np
 
 from .. import _lib
-from ..lidar_pr._batch import gpu, host, offsets, round256, stream, to_dev
-from ..lidar_pr.voxel import VoxelSizeError
+from ..lidar_pr import _batch
+from ..lidar_pr._batch import gpu, host, offsets, result_args, result_buffer, stream, to_dev
+from ..lidar_pr.voxel import VoxelSizeError, raise_failed
 from .visual_features import _Batch, _image
 from .visual_registration import _cameras
 
@@ -122,38 +123,11 @@ class _Frames:
                 self.t_cam.data_ptr(), b.n)
 
 
-def result_buffer(n, total, xyz_bytes, dev):
-    """ONE device byte buffer for everything a filter call returns, so that it comes back in one copy: (tensor, layout)."""
-    import torch
-    sizes = [round256(s) for s in (8 * (n + 1), 4 * n, xyz_bytes * 3 * total, 4 * total, 4 * total)]
-    lay = dict(zip(("out_off", "status", "rows", "rgb", "counts", "end"), (int(o) for o in offsets(sizes))))
-    return torch.zeros(max(lay["end"], 256), dtype=torch.uint8, device=dev), lay
-
-
-def result_args(t_out, lay, colors=True):
-    p = t_out.data_ptr()
-    return p + lay["rows"], p + lay["rgb"] if colors else None, p + lay["counts"], p + lay["out_off"], p + lay["status"]
-
-
 def unpack_result(host_bytes, lay, n, dtype, colors=True):
-    """The downloaded buffer as (points, colors or None, counts) per cloud, and the numbers of the clouds with status 1."""
-    out_off = host_bytes[lay["out_off"]:lay["out_off"] + 8 * (n + 1)].view(np.int64)
-    status = host_bytes[lay["status"]:lay["status"] + 4 * n].view(np.int32)
-    m, w = int(out_off[-1]), np.dtype(dtype).itemsize
-    xyz = host_bytes[lay["rows"]:lay["rows"] + 3 * w * m].view(dtype).reshape(m, 3)
-    rgb = unpack_colors(host_bytes[lay["rgb"]:lay["rgb"] + 4 * m].view(np.uint32)) if colors else None
-    cnt = host_bytes[lay["counts"]:lay["counts"] + 4 * m].view(np.int32)
-    res = []
-    for c in range(n):
-        a, b = int(out_off[c]), int(out_off[c + 1])
-        res.append(KeyframeCloud(xyz[a:b].copy(), rgb[a:b].copy() if colors else None, cnt[a:b].astype(np.int64)))
-    return res, [c for c in range(n) if status[c] != 0]
-
-
-def _raise_failed(res, failed):
-    if failed:
-        raise VoxelSizeError(failed, [None if c in failed else r for c, r in enumerate(res)])
-    return res
+    """The downloaded result buffer (`result_buffer` of lidar_pr/_batch.py) as a KeyframeCloud per cloud, and the numbers
+    of the clouds with status 1."""
+    res, failed = _batch.unpack_result(host_bytes, lay, n, dtype, colors)
+    return [KeyframeCloud(p, unpack_colors(w) if colors else None, k) for p, w, k in res], failed
 
 
 def _project(lib, f):
@@ -222,7 +196,7 @@ def voxel_subsample_batch(clouds, voxel_size=0.05, max_range=2.0, device=0):
         _lib.check(lib.cslam_cloud_voxel_dev(t_pts.data_ptr(), t_rgb.data_ptr() if colors else None, t_off.data_ptr(), n, v, r,
                                              *result_args(t_out, lay, colors), host(off), stream()))
         host_bytes = t_out.cpu().numpy()
-    return _raise_failed(*unpack_result(host_bytes, lay, n, np.float32, colors))
+    return raise_failed(*unpack_result(host_bytes, lay, n, np.float32, colors))
 
 
 def voxel_subsample(points, colors, voxel_size=0.05, max_range=2.0, device=0):

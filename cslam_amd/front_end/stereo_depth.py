@@ -22,9 +22,9 @@ import collections
 import numpy as np
 
 from .. import _lib
-from ..lidar_pr._batch import gpu, host, offsets, stream, to_dev
+from ..lidar_pr._batch import gpu, host, offsets, result_args, result_buffer, stream, to_dev
 from ..lidar_pr.voxel import VoxelSizeError
-from .keyframe_clouds import CLOUD_DEPTH_F32, _Frames, _leaf, _organised, _project, result_args, result_buffer, unpack_result
+from .keyframe_clouds import CLOUD_DEPTH_F32, _Frames, _leaf, _organised, _project, unpack_result
 from .visual_features import _Batch
 from .visual_stereo import _pairs, _parameters, _stereo_cameras
 

@@ -1,5 +1,7 @@
 """How a list of arrays becomes device memory with offsets, and how a lidar call reaches the GPU: shared by voxel.py, fpfh.py,
-robust.py, icp.py, icp_utils.py and keyframes.py.  Nothing else in lidar_pr builds offsets or packs an upload."""
+robust.py, icp.py, icp_utils.py and keyframes.py.  Nothing else in lidar_pr builds offsets or packs an upload.  Also the one
+result buffer of the voxel filters, which front_end/keyframe_clouds.py, front_end/stereo_depth.py and back_end/swarm_map.py
+use as voxel.py does."""
 import collections
 import contextlib
 import ctypes as C
@@ -61,6 +63,40 @@ def to_dev(arr, dev):
     import torch
     a = np.ascontiguousarray(arr)
     return torch.from_numpy(a if a.size else np.zeros(1, dtype=a.dtype)).to(dev)
+
+
+# ---- what a voxel filter call returns (lidar down-sampling, keyframe clouds, the swarm map): ONE device byte buffer, so that
+# everything comes back in one copy -------------------------------------------------------------------------------------
+def result_buffer(n, total, xyz_bytes, dev, colors=True, counts=True, extra_bytes=0):
+    """The buffer for `n` clouds of `total` input rows in all, with coordinates of `xyz_bytes` each: (tensor, layout), the
+    layout being the byte offsets of out_off, status, rows, rgb, counts and end.  A piece that is not wanted takes no room;
+    `extra_bytes` more follow at `end` for the caller's own use."""
+    import torch
+    sizes = [round256(s) for s in (8 * (n + 1), 4 * n, xyz_bytes * 3 * total, 4 * total if colors else 0, 4 * total if counts else 0)]
+    lay = dict(zip(("out_off", "status", "rows", "rgb", "counts", "end"), (int(o) for o in offsets(sizes))))
+    return torch.zeros(max(lay["end"] + extra_bytes, 256), dtype=torch.uint8, device=dev), lay
+
+
+def result_args(t_out, lay, colors=True, counts=True):
+    """Device pointers into the buffer, in the order the entry points take them: rows, rgb, counts, out_offsets, status."""
+    p = t_out.data_ptr()
+    return p + lay["rows"], p + lay["rgb"] if colors else None, p + lay["counts"] if counts else None, p + lay["out_off"], p + lay["status"]
+
+
+def unpack_result(host_bytes, lay, n, dtype, colors=True, counts=True):
+    """The downloaded buffer as (rows [m, 3] of `dtype`, packed colours uint32 [m] or None, counts int64 [m] or None) per
+    cloud, and the numbers of the clouds with status 1."""
+    out_off = host_bytes[lay["out_off"]:lay["out_off"] + 8 * (n + 1)].view(np.int64)
+    status = host_bytes[lay["status"]:lay["status"] + 4 * n].view(np.int32)
+    m, w = int(out_off[-1]), np.dtype(dtype).itemsize
+    xyz = host_bytes[lay["rows"]:lay["rows"] + 3 * w * m].view(dtype).reshape(m, 3)
+    rgb = host_bytes[lay["rgb"]:lay["rgb"] + 4 * m].view(np.uint32) if colors else None
+    cnt = host_bytes[lay["counts"]:lay["counts"] + 4 * m].view(np.int32) if counts else None
+    res = []
+    for c in range(n):
+        a, b = int(out_off[c]), int(out_off[c + 1])
+        res.append((xyz[a:b].copy(), rgb[a:b].copy() if colors else None, cnt[a:b].astype(np.int64) if counts else None))
+    return res, [c for c in range(n) if status[c] != 0]
 
 
 # What an enqueue function takes of a batch: `rows` and `d_off` are device pointers (the float64 rows of all arrays, their

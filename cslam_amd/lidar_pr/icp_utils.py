@@ -22,7 +22,7 @@ open3d's documented algorithm.
 
 Clouds are [n, >=3] arrays or anything with a `.points` attribute (an open3d cloud); they are widened to float64 and
 rows with a non-finite coordinate are dropped, as the reference's `downsample` does.  The clouds the handler stores
-and sends are down-sampled ones: `downsample` / `downsample_clouds` (voxel.py over csrc/voxel.hip), and
+and sends are down-sampled ones: `downsample` / `downsample_clouds` (voxel.py over csrc/cloud.hip and csrc/voxel.hip), and
 `keyframes.ingest` does it on the upload the ScanContext descriptor uses.
 
 Yaw seed: with `matcher.add_item(descriptor(dst))`, `matcher.search(descriptor(src))`, a source that is the target

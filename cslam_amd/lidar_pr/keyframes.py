@@ -29,10 +29,10 @@ def ingest(clouds, voxel_size, device=0):
         desc_bytes = 8 * n * RINGS * SECTORS
         cl = upload(clouds, dev)
         t_out, lay = voxel.enqueue(lib, cl, voxel_size, False, extra_bytes=desc_bytes + 256)
-        base = t_out.data_ptr() + lay["extra"]
+        base = t_out.data_ptr() + lay["end"]
         scancontext.enqueue(lib, cl.rows, cl.d_off, n, RINGS, SECTORS, MAX_LENGTH, base, base + desc_bytes)
         host = t_out.cpu().numpy()
-    at = lay["extra"]
+    at = lay["end"]
     err = scancontext.status_error(int(host[at + desc_bytes:at + desc_bytes + 4].view(np.int32)[0]), SECTORS)
     if err is not None:
         raise err

@@ -1,28 +1,24 @@
-"""Batched voxel down-sampling of keyframe clouds (csrc/voxel.hip behind `cslam_voxel_downsample_dev`): the counterpart of
+"""Batched voxel down-sampling of keyframe clouds (`cslam_voxel_downsample_dev`: the filter chain of csrc/cloud.hip with
+open3d's rule of csrc/cloud.h, on the engine of csrc/voxel.hip): the counterpart of
 the reference's `downsample` (icp_utils.py:93-100, open3d's `voxel_down_sample`).  `enqueue` and `unpack` are the two
 halves `keyframes.ingest` shares with `downsample_clouds`."""
 import numpy as np
 
 from .. import _lib
-from ._batch import gpu, host, offsets, round256, rows, stream, upload
+from ._batch import gpu, host, result_args, result_buffer, rows, stream, unpack_result, upload
 
 VOXEL_TILE = 2048        # keys per workgroup per radix pass of the voxel sort (csrc/voxel_plan.h); the tests size around it
 VOXEL_SEG_BLOCK = 256    # threads per workgroup of the kernel that sums a voxel's points (one wave per voxel)
 
 
 def enqueue(lib, cl, voxel_size, counts, extra_bytes=0):
-    """`cslam_voxel_downsample_dev` on uploaded clouds.  Every result lies in ONE device byte buffer, so that it comes
-    back in one copy: returns (buffer, layout) with layout = byte offsets of out_offsets, status, rows, counts, extra."""
-    import torch
+    """`cslam_voxel_downsample_dev` on uploaded clouds.  Every result lies in the one result buffer of `_batch`, with
+    `extra_bytes` of the caller's own behind it at layout["end"]: returns (buffer, layout)."""
     n, total = len(cl.off) - 1, int(cl.off[-1])
-    sizes = [round256(b) for b in (8 * (n + 1), 4 * n, 24 * total, 4 * total if counts else 0)]
-    lay = dict(zip(("out_off", "status", "rows", "counts", "extra"), (int(o) for o in offsets(sizes))))
-    t_out = torch.zeros(lay["extra"] + extra_bytes, dtype=torch.uint8, device=cl.buf.device)
-    base = t_out.data_ptr()
-    _lib.check(lib.cslam_voxel_downsample_dev(
-        cl.rows if total else None, cl.d_off, n, float(voxel_size),
-        base + lay["rows"] if total else None, base + lay["out_off"], base + lay["counts"] if counts and total else None,
-        base + lay["status"], host(cl.off), stream()))
+    t_out, lay = result_buffer(n, total, 8, cl.buf.device, colors=False, counts=counts, extra_bytes=extra_bytes)
+    p_rows, _, p_counts, p_out_off, p_status = result_args(t_out, lay, colors=False, counts=counts)
+    _lib.check(lib.cslam_voxel_downsample_dev(cl.rows if total else None, cl.d_off, n, float(voxel_size), p_rows, p_out_off, p_counts,
+                                              p_status, host(cl.off), stream()))
     return t_out, lay
 
 
@@ -38,22 +34,17 @@ class VoxelSizeError(ValueError):
         self.clouds = clouds
 
 
-def unpack(host_bytes, lay, n, counts):
-    """Split the downloaded result buffer into per-cloud arrays; raises VoxelSizeError for a status of 1."""
-    out_off = host_bytes[lay["out_off"]:lay["out_off"] + 8 * (n + 1)].view(np.int64)
-    status = host_bytes[lay["status"]:lay["status"] + 4 * n].view(np.int32)
-    m = int(out_off[-1])
-    means = host_bytes[lay["rows"]:lay["rows"] + 24 * m].view(np.float64).reshape(m, 3)
-    cnt = host_bytes[lay["counts"]:lay["counts"] + 4 * m].view(np.int32) if counts else None
-    res = []
-    for c in range(n):
-        a, b = int(out_off[c]), int(out_off[c + 1])
-        pts = means[a:b].copy()
-        res.append((pts, cnt[a:b].astype(np.int64)) if counts else pts)
-    failed = [c for c in range(n) if status[c] != 0]
+def raise_failed(res, failed):
+    """`res` as it is, or VoxelSizeError with None in the places of the `failed` clouds."""
     if failed:
         raise VoxelSizeError(failed, [None if c in failed else r for c, r in enumerate(res)])
     return res
+
+
+def unpack(host_bytes, lay, n, counts):
+    """Split the downloaded result buffer into per-cloud arrays; raises VoxelSizeError for a status of 1."""
+    res, failed = unpack_result(host_bytes, lay, n, np.float64, colors=False, counts=counts)
+    return raise_failed([(pts, cnt) if counts else pts for pts, _, cnt in res], failed)
 
 
 def downsample_clouds(clouds, voxel_size, counts=False, device=0):

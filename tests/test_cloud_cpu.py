@@ -4,7 +4,8 @@
   * the constants in Python mirror csrc/cloud.h
   * the facts about tests/cloud_reference.py that tests/test_cloud_gpu.py rests on, each asserted and printed
   * csrc/cloud.h and the plan (csrc/voxel_plan.h) as a stand-alone program under -fsanitize=address,undefined, whose
-    projected points are compared with the numpy restatement bit for bit (never loaded into Python)
+    projected points are compared with the numpy restatement bit for bit (never loaded into Python); in the same program
+    the open3d rule of the lidar filter (GridOpen3d) against the indices of icp_reference.voxel_average
 """
 import ctypes as C
 import os
@@ -272,7 +273,37 @@ template <typename S> static size_t write_head(int n_clouds, int64_t n_pts, int6
     return sum + bytes;
 }
 
-int main() {
+// open3d's rule on the clouds of a file (per cloud: int64 n, double voxel, n rows of 3 doubles): "G status bx by bz", then
+// per row "P ix iy iz key".  The bounds are taken as the bounds kernel takes them; a refused cloud prints no rows.
+static void open3d_clouds(const char *path) {
+    FILE *fp = fopen(path, "rb");
+    if (!fp) { printf("no clouds file\n"); exit(1); }
+    int64_t n;
+    while (fread(&n, 8, 1, fp) == 1) {
+        double voxel;
+        if (fread(&voxel, 8, 1, fp) != 1) exit(1);
+        double *p = (double *)malloc((size_t)(n ? n : 1) * 24);
+        if (fread(p, 24, (size_t)n, fp) != (size_t)n) exit(1);
+        double lo[3] = {INFINITY, INFINITY, INFINITY}, hi[3] = {-INFINITY, -INFINITY, -INFINITY}, base[3];
+        for (int64_t i = 0; i < n; ++i)
+            for (int a = 0; a < 3; ++a) { lo[a] = fmin(lo[a], p[3 * i + a]); hi[a] = fmax(hi[a], p[3 * i + a]); }
+        const GridOpen3d::P g = {voxel, voxel / 2.0};
+        int b[3];
+        const int over = GridOpen3d::range(lo, hi, g, base, b);
+        printf("G %d %d %d %d\n", over, b[0], b[1], b[2]);
+        for (int64_t i = 0; i < n && !over; ++i) {
+            uint32_t k[3];
+            for (int a = 0; a < 3; ++a) k[a] = GridOpen3d::index(p[3 * i + a], g, base[a]);
+            printf("P %u %u %u %llx\n", k[0], k[1], k[2],
+                   (unsigned long long)GridOpen3d::key(k[0], k[1], k[2], b[1] + b[2 - GridOpen3d::MAJOR], b[2 - GridOpen3d::MAJOR]));
+        }
+        free(p);
+    }
+    fclose(fp);
+}
+
+int main(int argc, char **argv) {
+    if (argc > 1) open3d_clouds(argv[1]);
     // projected points of a small frame in both depth types, for the comparison with the numpy restatement
     const double cam[4] = {60.0, 61.0, 31.5, 23.5};
     float k[4], p[3];
@@ -350,10 +381,10 @@ def _sanitizer_flags(cxx, tmp_path):
     pytest.skip("this compiler has no sanitizer runtime")
 
 
-def test_cloud_header_under_sanitizers(tmp_path):
-    """cloud.h and the plan in a stand-alone program with its own main, built with -fsanitize=address,undefined: the
-    projection in both depth types (compared with the restatement bit for bit), the range rule at its edges, every piece of
-    every scratch layout written to its full length.  Not loaded into Python."""
+@pytest.fixture(scope="module")
+def cloud_main(tmp_path_factory):
+    """The stand-alone program, built once with -fsanitize=address,undefined."""
+    tmp_path = tmp_path_factory.mktemp("cloud_main")
     cxx = _cxx()
     flags = _sanitizer_flags(cxx, tmp_path)
     (tmp_path / "cloud_main.cpp").write_text(CLOUD_MAIN)
@@ -361,7 +392,66 @@ def test_cloud_header_under_sanitizers(tmp_path):
     r = subprocess.run([cxx, "-O1", "-g", "-std=c++17", "-fno-sanitize-recover=all", "-I", CSRC, str(tmp_path / "cloud_main.cpp"), "-o", str(exe)]
                        + flags, capture_output=True, text=True)
     assert r.returncode == 0, r.stderr
-    r = subprocess.run([str(exe)], capture_output=True, text=True)
+    return exe
+
+
+def _open3d_clouds():
+    """(cloud, voxel) pairs for the open3d rule: seeded rows with negative coordinates, rows exactly on cell faces, one row,
+    all three axes at the widest index a key holds (shifts of 42 and 21), a span of 2^21 - 1 cells and one of 2^21."""
+    rng = np.random.default_rng(33)
+    faces = np.concatenate([[[-1.75, -1.75, -1.75]], rng.integers(-3, 5, (200, 3)) * 0.5])      # minimum -1.75: faces at multiples of 0.5
+    top = (2 ** 21 - 1) * 0.5
+    wide = np.concatenate([[[0.0, 0.0, 0.0], [top, top, top]], rng.integers(0, 2 ** 21, (60, 3)) * 0.5])
+    return [(rng.uniform(-3.0, 2.0, (300, 3)), 0.3), (faces, 0.5), (np.array([[0.1, -7.0, 3.0]]), 0.5), (wide, 0.5),
+            (np.array([[0.0, 0.0, 0.0], [0.0, top, 0.0]]), 0.5), (np.array([[0.0, 0.0, 0.0], [0.0, 2 ** 21 * 0.5, 0.0]]), 0.5)]
+
+
+def test_open3d_rule_under_sanitizers(cloud_main, tmp_path):
+    """GridOpen3d's range, index and key in the stand-alone program against the indices of icp_reference.voxel_average:
+    the same integers row by row, keys that pack them with the cloud's own widths, and, grouped by those keys in key order,
+    voxel_average's very rows."""
+    import icp_reference
+    clouds = _open3d_clouds()
+    with open(tmp_path / "clouds.bin", "wb") as fp:
+        for pts, voxel in clouds:
+            fp.write(np.int64(len(pts)).tobytes() + np.float64(voxel).tobytes() + np.ascontiguousarray(pts, dtype=np.float64).tobytes())
+    r = subprocess.run([str(cloud_main), str(tmp_path / "clouds.bin")], capture_output=True, text=True)
+    assert r.returncode == 0, r.stdout + r.stderr
+    lines = [ln.split() for ln in r.stdout.splitlines()]
+    heads = [k for k, ln in enumerate(lines) if ln[0] == "G"]
+    assert len(heads) == len(clouds)
+    statuses = []
+    for (pts, voxel), at in zip(clouds, heads):
+        origin = pts.min(axis=0) - voxel / 2.0                                      # voxel_average's own two lines
+        want = np.floor((pts - origin) / voxel).astype(np.int64)
+        over = int((want.max(axis=0) >= 2 ** 21).any())
+        statuses.append(over)
+        bits = [0 if over and q >= 2 ** 21 else int(q).bit_length() for q in want.max(axis=0)]
+        assert [int(x) for x in lines[at][1:]] == [over] + bits, lines[at]
+        rows = lines[at + 1:at + 1 + len(pts)]
+        if over:
+            assert at + 1 == len(lines) or lines[at + 1][0] != "P"
+            continue
+        assert all(ln[0] == "P" for ln in rows) and len(rows) == len(pts)
+        got = np.array([[int(x) for x in ln[1:4]] for ln in rows], dtype=np.int64)
+        assert np.array_equal(got, want)
+        keys = [int(ln[4], 16) for ln in rows]
+        assert keys == [(int(i) << (bits[1] + bits[2])) | (int(j) << bits[2]) | int(k) for i, j, k in want]
+        uniq, inv, cnt = np.unique(np.array(keys, dtype=np.uint64), return_inverse=True, return_counts=True)
+        out = np.zeros((len(uniq), 3))
+        np.add.at(out, inv.reshape(-1), pts)
+        assert np.array_equal(out / cnt[:, None], icp_reference.voxel_average(pts, voxel))
+    assert statuses == [0, 0, 0, 0, 0, 1]
+    assert lines[heads[3]][1:] == ["0", "21", "21", "21"] and lines[heads[4]][1:] == ["0", "0", "21", "0"]
+    faces = clouds[1][0]
+    assert np.array_equal((faces[1:] + 2.0) / 0.5, np.floor((faces[1:] + 2.0) / 0.5))      # origin -2: those rows ARE on cell faces
+
+
+def test_cloud_header_under_sanitizers(cloud_main):
+    """cloud.h and the plan in a stand-alone program with its own main, built with -fsanitize=address,undefined: the
+    projection in both depth types (compared with the restatement bit for bit), the range rule at its edges, every piece of
+    every scratch layout written to its full length.  Not loaded into Python."""
+    r = subprocess.run([str(cloud_main)], capture_output=True, text=True)
     assert r.returncode == 0, r.stdout + r.stderr
     assert "cloud ok:" in r.stdout
     lines = [ln.split() for ln in r.stdout.splitlines()]

@@ -245,3 +245,146 @@ def test_scratch_is_carved_afresh_for_every_batch(vox):
         runs = [raw(small), raw(large), raw(small)]
     assert runs[0] == first and runs[2] == first and runs[1] == raw(large)
     assert first.startswith(ref.voxel_average(small[0], VOXEL).tobytes())
+
+
+# ---- the lidar call as a caller of the one filter chain (csrc/cloud.hip) ------------------------------------------------
+def _raw_call(clouds, voxel, host_offsets=True, device_offsets=None):
+    """`cslam_voxel_downsample_dev` through `_lib` directly: (return code, every output as bytes).  `device_offsets`
+    replaces the offsets on the device; the host copy is given or not."""
+    import ctypes as C
+    import torch
+    from cslam_amd import _lib
+    from cslam_amd.lidar_pr._batch import stream, to_dev, upload
+    lib = _lib.load()
+    dev = torch.device("cuda", 0)
+    cl = upload([np.ascontiguousarray(c, dtype=np.float64) for c in clouds], dev)
+    n, total = len(clouds), int(cl.off[-1])
+    d_off = cl.d_off if device_offsets is None else to_dev(np.asarray(device_offsets, dtype=np.int64), dev)
+    outs = [torch.zeros(max(k, 1), dtype=torch.uint8, device=dev) for k in (24 * total, 8 * (n + 1), 4 * total, 4 * n)]
+    rc = lib.cslam_voxel_downsample_dev(cl.rows, d_off if isinstance(d_off, int) else d_off.data_ptr(), n, float(voxel),
+                                        outs[0].data_ptr(), outs[1].data_ptr(), outs[2].data_ptr(), outs[3].data_ptr(),
+                                        cl.off.ctypes.data_as(C.c_void_p) if host_offsets else None, stream())
+    torch.cuda.synchronize()
+    return rc, [o.cpu().numpy().tobytes() for o in outs]
+
+
+def _lattice_cloud(rng, bits):
+    """At most 64 rows on the voxel lattice (voxel 0.5, minimum 0: a row's index is its coordinate / 0.5) whose largest
+    index on axis a is 2^bits[a] - 1: the origin, the top index on each axis, all three at once, seeded rows and a few
+    second rows inside the same voxels."""
+    top = np.array([2 ** b - 1 for b in bits])
+    idx = rng.integers(0, top + 1, (40, 3))
+    for a in range(3):
+        idx[a, a] = top[a]
+    pts = np.concatenate([[[0, 0, 0], top], idx]).astype(np.float64) * VOXEL
+    pts = np.concatenate([pts, pts[5:20] + 0.125])
+    return pts[rng.permutation(len(pts))]
+
+
+def test_key_shifts_at_and_across_32_bits(vox):
+    """Keys are packed from 32-bit shifts: per-cloud widths whose shifts (by + bz, bz) sit below, at and beyond 32."""
+    rng = np.random.default_rng(77)
+    widths = [(3, 21, 10), (3, 21, 11), (3, 12, 21), (3, 21, 21)]
+    clouds = [_lattice_cloud(rng, b) for b in widths]
+    for c, b in zip(clouds, widths):
+        assert len(c) <= 64 and keys_of(c, VOXEL).max(axis=0).tolist() == [2 ** k - 1 for k in b]
+    assert [(b[1] + b[2], b[2]) for b in widths] == [(31, 10), (32, 11), (33, 21), (42, 21)]
+    want = [ref.voxel_average(c, VOXEL) for c in clouds]
+    assert all(len(w) == 42 for w in want)                  # 57 rows, 15 of them second rows of a voxel
+    for c, w in zip(clouds, want):
+        assert same(vox.downsample(c, VOXEL), w)
+    for g, w in zip(vox.downsample_clouds(clouds, VOXEL), want):      # per-cloud widths differ inside one launch
+        assert same(g, w)
+
+
+def test_without_host_offsets(vox):
+    """h_offsets == NULL: the bounds pass runs on offsets the host has not seen, which are read back before the one wait
+    and checked after it.  Same bytes as with host offsets; decreasing device offsets are refused with the usual message
+    after a bounds pass that stayed inside the rows."""
+    from cslam_amd import _lib
+    rng = np.random.default_rng(78)
+    big = rng.uniform(-1.0, 1.0, (vox.VOXEL_TILE + 1, 3))
+    big[17] = [0.0, np.nan, 0.0]
+    clouds = [np.zeros((0, 3)), rng.uniform(-1.0, 1.0, (1, 3)), big]
+    rc_h, with_host = _raw_call(clouds, VOXEL, True)
+    rc_d, without = _raw_call(clouds, VOXEL, False)
+    assert rc_h == 0 and rc_d == 0
+    assert without == with_host
+    n_out = np.frombuffer(with_host[1], dtype=np.int64)
+    assert n_out[:3].tolist() == [0, 0, 1] and n_out[3] == 1 + len(ref.voxel_average(big, VOXEL))
+    got = np.frombuffer(with_host[0], dtype=np.float64).reshape(-1, 3)[1:n_out[3]]
+    assert same(got, ref.voxel_average(big, VOXEL))
+    total = len(big) + 1
+    rc, _ = _raw_call(clouds, VOXEL, False, device_offsets=[0, total, 1, total])      # every row read is a row of the buffer
+    assert rc == -1 and _lib.load().cslam_last_error() == b"invalid argument: offsets must not decrease"
+    rc, again = _raw_call(clouds, VOXEL, False)                                         # and the next call is not affected
+    assert rc == 0 and again == with_host
+
+
+def _plan_info(n, n_clouds, key_bits):
+    T = 2048
+    return [-(-key_bits // 8), -(-(n_clouds - 1).bit_length() // 8), key_bits, -(-n // T)]
+
+
+def test_profiles_of_the_lidar_and_the_cloud_calls_do_not_mix(vox):
+    """One profile type, two instances: each read gives the stage times and the plan of the last call of its own family,
+    whatever the other family ran in between."""
+    import ctypes as C
+    from cslam_amd import _lib
+    from cslam_amd.front_end import keyframe_clouds as kc
+    lib = _lib.load()
+    rng = np.random.default_rng(79)
+    lidar = _lattice_cloud(rng, (3, 5, 4))[:40]
+    lidar = np.concatenate([lidar, rng.integers(0, 8, (vox.VOXEL_TILE + 1 - 40, 3)) * VOXEL])      # two sort tiles, 12 key bits
+    assert keys_of(lidar, VOXEL).max(axis=0).tolist() == [7, 31, 15]
+    small = (rng.integers(0, 4, (50, 3)) * 0.5).astype(np.float32)                  # one tile; PCL rule, leaf 0.5: 2 bits an axis
+    small[:2] = [[0, 0, 0], [1.5, 1.5, 1.5]]
+
+    def read(fn, k):
+        ms, info = (C.c_double * k)(), (C.c_int32 * 4)()
+        _lib.check(fn(C.byref(ms), C.byref(info)))
+        assert all(np.isfinite(t) and t >= 0.0 for t in ms)
+        return list(info)
+
+    _lib.check(lib.cslam_voxel_profile(1))
+    _lib.check(lib.cslam_cloud_profile(1))
+    try:
+        want = vox.downsample(lidar, VOXEL)
+        kc.voxel_subsample(small, None, 0.5, 10.0)
+        assert read(lib.cslam_voxel_profile_read, 6) == _plan_info(len(lidar), 1, 12)
+        assert read(lib.cslam_cloud_profile_read, 7) == _plan_info(len(small), 1, 6)
+        kc.voxel_subsample(small, None, 0.5, 10.0)
+        assert same(vox.downsample(lidar, VOXEL), want)
+        assert read(lib.cslam_cloud_profile_read, 7) == _plan_info(len(small), 1, 6)
+        assert read(lib.cslam_voxel_profile_read, 6) == _plan_info(len(lidar), 1, 12)
+    finally:
+        _lib.check(lib.cslam_voxel_profile(0))
+        _lib.check(lib.cslam_cloud_profile(0))
+    assert same(want, ref.voxel_average(lidar, VOXEL))
+    assert lib.cslam_voxel_profile_read(C.byref((C.c_double * 6)()), C.byref((C.c_int32 * 4)())) == -1      # switched off: nothing to read
+
+
+def test_lidar_and_keyframe_cloud_calls_share_their_scratch(vox):
+    """One stream, one pair of scratch blocks for both families: a lidar call of VOXEL_TILE + 1 points, a keyframe-cloud
+    call of 8 x 8 pixels, the lidar call again.  All three equal what they give alone, byte for byte."""
+    import torch
+    import cloud_reference as cref
+    from cslam_amd.front_end import keyframe_clouds as kc
+    rng = np.random.default_rng(80)
+    lidar = [rng.uniform(-1.0, 1.0, (vox.VOXEL_TILE + 1, 3))]
+    img, depth = cref.scene_image(8, 8), cref.scene_depth(8, 8)
+
+    def raw_lidar():
+        return b"".join(g.tobytes() + c.tobytes() for g, c in vox.downsample_clouds(lidar, VOXEL, counts=True))
+
+    def raw_frame():
+        c = kc.keyframe_clouds([img], [depth], cref.SCENE_CAMERA, 0.05, 2.0)[0]
+        return c.points.tobytes() + c.colors.tobytes() + c.counts.tobytes()
+
+    alone = [raw_lidar(), raw_frame()]
+    assert alone[0].startswith(ref.voxel_average(lidar[0], VOXEL).tobytes())
+    want = cref.keyframe_cloud(img, depth, cref.SCENE_CAMERA, 0.05, 2.0)
+    assert len(want[0]) > 0 and alone[1].startswith(want[0].tobytes())
+    with torch.cuda.stream(torch.cuda.Stream()):
+        runs = [raw_lidar(), raw_frame(), raw_lidar()]
+    assert runs == [alone[0], alone[1], alone[0]]

@@ -88,6 +88,22 @@ struct DeviceOnce {
 };
 int cslam_cu_count();          // compute units of the CURRENT device, cached per device (bank.hip); 0 on error
 
+// A kernel whose dynamic LDS exceeds the 64 KB a launch gets by default: the attribute once per device, the launch, its error.  The
+// latch is a function-local static of the instantiation, so there is one per kernel:
+//     if (pool) return launch_lds<kernel<true>>(grid, block, lds, st, args);
+template <auto Kernel, class Args>
+static int launch_lds(dim3 grid, dim3 block, int lds, hipStream_t st, const Args &args) {
+    static DeviceOnce once;
+    int dev;
+    if (once.todo(&dev)) {
+        HIP_TRY(hipFuncSetAttribute((const void *)Kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
+        once.done(dev);
+    }
+    hipLaunchKernelGGL(Kernel, grid, block, lds, st, args);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
 // Scratch of an entry point that needs device memory between its own kernels (split-K partial sums, operand pairs): one
 // grow-only buffer per (device, stream).  Launches on ONE stream run in order, so they can share a buffer; two streams -- two
 // extraction lanes, two host threads -- must not.  A superseded buffer stays allocated: a pointer captured in a hipGraph (the

@@ -31,6 +31,7 @@
 #include <hip/hip_fp16.h>
 #include "common.h"
 #include "pairs.h"
+#include "direct_dev.h"
 
 typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -105,16 +106,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_direct_h_kernel(ConvDirectArgs
     const float sx = XP ? scale_in_2p13_2p14(amax) : scale_le_32752(amax);
     const float inv = p.inv_sw / sx;
 
-    // Blocks to workgroups, XCD-aware (as conv_stem_direct_h.hip): workgroup w runs on XCD w % 8, every XCD has its own L2; each XCD
-    // takes one contiguous eighth of the blocks and its workgroups walk it side by side, so that the halo a block shares with its
-    // neighbours is read through ONE L2 at about the same time (block b -> workgroup b % grid: the halo came through two or three)
-    const bool by_xcd = (gridDim.x & 7) == 0;
-    const int wg_xcd = by_xcd ? (int)blockIdx.x & 7 : 0, wg_j = by_xcd ? (int)blockIdx.x >> 3 : (int)blockIdx.x;
-    const int wg_per = by_xcd ? (int)gridDim.x >> 3 : (int)gridDim.x;
-    const int per_xcd = by_xcd ? (p.nblk + 7) >> 3 : p.nblk;
-    const int blk_beg = wg_xcd * per_xcd;
-    const int blk_cnt = min(per_xcd, p.nblk - blk_beg);
-    const int n_mine = blk_cnt > wg_j ? (blk_cnt - wg_j + wg_per - 1) / wg_per : 0;
+    // blocks to workgroups by XCD (direct_dev.h)
+    const DirectPart part = direct_partition(p.nblk);
+    const int wg_j = part.wg_j, wg_per = part.wg_per, blk_beg = part.blk_beg, n_mine = part.n_mine;
     if (n_mine <= 0) return;
     const int nslabs_total = n_mine * p.nslab;
 
@@ -560,14 +554,7 @@ __global__ __launch_bounds__(512, 2) void conv3x3_direct_h_kernel(ConvDirectArgs
 #endif
 
     if (p.amax_out) {
-        unsigned *s_amax = (unsigned *)cd_smem;
-        if (tid == 0) *s_amax = 0u;
-        __syncthreads();
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) my_amax = fmaxf(my_amax, __shfl_xor(my_amax, o, 64));
-        if (lane == 0) atomicMax(s_amax, __float_as_uint(my_amax));
-        __syncthreads();
-        if (tid == 0 && *s_amax > *(volatile unsigned *)p.amax_out) atomicMax(p.amax_out, *s_amax);
+        amax_publish(my_amax, p.amax_out, cd_smem, tid, lane);
     }
 }
 
@@ -602,54 +589,31 @@ static int conv_direct_h_launch(const float *d_x, const void *d_w2, const float 
 #endif
     const int grid = (int)(nblk < n_cu ? nblk : n_cu);
     hipStream_t st = (hipStream_t)stream;
-#define CD_LAUNCH(R, P) do { \
-        static DeviceOnce once; int once_dev; \
-        if (once.todo(&once_dev)) { \
-            HIP_TRY(hipFuncSetAttribute((const void *)conv3x3_direct_h_kernel<R, P>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS)); \
-            once.done(once_dev); } \
-        hipLaunchKernelGGL((conv3x3_direct_h_kernel<R, P>), dim3(grid), dim3(512), CD_LDS, st, a); } while (0)
+    const dim3 g(grid), b(512);
 #ifdef CSLAM_ABLATIONS
     if (const char *e = getenv("CSLAM_CD_DBG")) {              // timing-only ablations (wrong results): measurement build
         const int d = atoi(e);
-#define CD_LAUNCH_D1(D, P) do { HIP_TRY(hipFuncSetAttribute((const void *)conv3x3_direct_h_kernel<true, P, D>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS)); \
-        hipLaunchKernelGGL((conv3x3_direct_h_kernel<true, P, D>), dim3(grid), dim3(512), CD_LDS, st, a); HIP_TRY(hipGetLastError()); return CSLAM_OK; } while (0)
-#define CD_LAUNCH_D(D) do { if (pool) CD_LAUNCH_D1(D, true); else CD_LAUNCH_D1(D, false); } while (0)
-        if (d == 1) CD_LAUNCH_D(1);
-        if (d == 2) CD_LAUNCH_D(2);
-        if (d == 3) CD_LAUNCH_D(3);
-        if (d == 7) CD_LAUNCH_D(7);
-        if (d == 11) CD_LAUNCH_D(11);
-        if (d == 15) CD_LAUNCH_D(15);
-        if (d == 32) CD_LAUNCH_D(32);
-        if (d == 64) CD_LAUNCH_D(64);
-        if (d == 16 && !pool) { HIP_TRY(hipFuncSetAttribute((const void *)conv3x3_direct_h_kernel<true, false, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS));
-                       hipLaunchKernelGGL((conv3x3_direct_h_kernel<true, false, 0, true>), dim3(grid), dim3(512), CD_LDS, st, a); HIP_TRY(hipGetLastError()); return CSLAM_OK; }
-#undef CD_LAUNCH_D1
-#undef CD_LAUNCH_D
+        auto dbg = [&](auto d_tag) {
+            constexpr int D = decltype(d_tag)::value;
+            return pool ? launch_lds<conv3x3_direct_h_kernel<true, true, D>>(g, b, CD_LDS, st, a) : launch_lds<conv3x3_direct_h_kernel<true, false, D>>(g, b, CD_LDS, st, a);
+        };
+        if (d == 1) return dbg(std::integral_constant<int, 1>{});
+        if (d == 2) return dbg(std::integral_constant<int, 2>{});
+        if (d == 3) return dbg(std::integral_constant<int, 3>{});
+        if (d == 7) return dbg(std::integral_constant<int, 7>{});
+        if (d == 11) return dbg(std::integral_constant<int, 11>{});
+        if (d == 15) return dbg(std::integral_constant<int, 15>{});
+        if (d == 32) return dbg(std::integral_constant<int, 32>{});
+        if (d == 64) return dbg(std::integral_constant<int, 64>{});
+        if (d == 16 && !pool) return launch_lds<conv3x3_direct_h_kernel<true, false, 0, true>>(g, b, CD_LDS, st, a);
     }
 #endif
-    if (x_pairs) {
-#define CD_LAUNCH_P(R, P) do { \
-        static DeviceOnce once; int once_dev; \
-        if (once.todo(&once_dev)) { \
-            HIP_TRY(hipFuncSetAttribute((const void *)conv3x3_direct_h_kernel<R, P, 0, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, CD_LDS)); \
-            once.done(once_dev); } \
-        hipLaunchKernelGGL((conv3x3_direct_h_kernel<R, P, 0, false, true>), dim3(grid), dim3(512), CD_LDS, st, a); } while (0)
-        if (relu && pool) CD_LAUNCH_P(true, true);
-        else if (relu) CD_LAUNCH_P(true, false);
-        else if (pool) CD_LAUNCH_P(false, true);
-        else CD_LAUNCH_P(false, false);
-#undef CD_LAUNCH_P
-        HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+    if (x_pairs) {                                             // <ReLU, pooling, DBG, PIXA, pair-format input>
+        if (relu) return pool ? launch_lds<conv3x3_direct_h_kernel<true, true, 0, false, true>>(g, b, CD_LDS, st, a) : launch_lds<conv3x3_direct_h_kernel<true, false, 0, false, true>>(g, b, CD_LDS, st, a);
+        return pool ? launch_lds<conv3x3_direct_h_kernel<false, true, 0, false, true>>(g, b, CD_LDS, st, a) : launch_lds<conv3x3_direct_h_kernel<false, false, 0, false, true>>(g, b, CD_LDS, st, a);
     }
-    if (relu && pool) CD_LAUNCH(true, true);
-    else if (relu) CD_LAUNCH(true, false);
-    else if (pool) CD_LAUNCH(false, true);
-    else CD_LAUNCH(false, false);
-#undef CD_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return CSLAM_OK;
+    if (relu) return pool ? launch_lds<conv3x3_direct_h_kernel<true, true>>(g, b, CD_LDS, st, a) : launch_lds<conv3x3_direct_h_kernel<true, false>>(g, b, CD_LDS, st, a);
+    return pool ? launch_lds<conv3x3_direct_h_kernel<false, true>>(g, b, CD_LDS, st, a) : launch_lds<conv3x3_direct_h_kernel<false, false>>(g, b, CD_LDS, st, a);
 }
 CSLAM_API int cslam_conv3x3_direct_h_dev(const float *d_x, const void *d_w2, const float *d_bias, int B, int H, int W, int Cin,
                                          int Cout, int relu, int pool, const unsigned *d_amax, float inv_sw,

@@ -29,6 +29,7 @@
 #include <hip/hip_fp16.h>
 #include "common.h"
 #include "pairs.h"
+#include "direct_dev.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
@@ -86,17 +87,12 @@ __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDir
     }
     if (RES == 2) inv_sres = 1.0f / scale_in_2p13_2p14(__uint_as_float(*p.res_bound));
     const float floor_ = p.relu ? 0.0f : -INFINITY;
-    float neg1 = -1.0f;                                        // (a run-time value: with the literal hipcc folds fma(h, -1, u) into a conversion and a subtraction)
+    float neg1 = -1.0f;                                        // (a run-time value: pair_store4, direct_dev.h)
     asm volatile("" : "+v"(neg1));
 
-    // blocks to workgroups by XCD (contiguous eighths: the halo neighbours share goes through one L2)
-    const bool by_xcd = (gridDim.x & 7) == 0;
-    const int wg_xcd = by_xcd ? (int)blockIdx.x & 7 : 0, wg_j = by_xcd ? (int)blockIdx.x >> 3 : (int)blockIdx.x;
-    const int wg_per = by_xcd ? (int)gridDim.x >> 3 : (int)gridDim.x;
-    const int per_xcd = by_xcd ? (p.nblk + 7) >> 3 : p.nblk;
-    const int blk_beg = wg_xcd * per_xcd;
-    const int blk_cnt = min(per_xcd, p.nblk - blk_beg);
-    const int n_mine = blk_cnt > wg_j ? (blk_cnt - wg_j + wg_per - 1) / wg_per : 0;
+    // blocks to workgroups by XCD (direct_dev.h)
+    const DirectPart part = direct_partition(p.nblk);
+    const int wg_j = part.wg_j, wg_per = part.wg_per, blk_beg = part.blk_beg, n_mine = part.n_mine;
     if (n_mine <= 0) return;
 
     // ---- this wave's weights: [tap][32-channel K step][hi | lo], register-resident for the whole kernel (conv_stem_direct_h.hip)
@@ -282,14 +278,7 @@ __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDir
         int off = eo.pix + (row0 + r) * rowB + (OUTP ? ch_pair : ch_f32);
         off = row0 + r < eo.rows ? off : DP_OOB;
         if (OUTP) {
-            const float u0 = ev[0] * s_out, u1 = ev[1] * s_out, u2 = ev[2] * s_out, u3 = ev[3] * s_out;
-            const unsigned h01 = pack_half2(u0, u1), h23 = pack_half2(u2, u3);
-            const unsigned l01 = pack_half2(fma_half<0>(h01, neg1, u0), fma_half<1>(h01, neg1, u1));
-            const unsigned l23 = pack_half2(fma_half<0>(h23, neg1, u2), fma_half<1>(h23, neg1, u3));
-            if (!(DBG & 16)) {
-                __builtin_amdgcn_raw_buffer_store_b64((u32x2){h01, h23}, rsY, off, 0, 0);
-                __builtin_amdgcn_raw_buffer_store_b64((u32x2){l01, l23}, rsY, off, 64, 0);
-            } else asm volatile("" :: "v"(h01), "v"(h23), "v"(l01), "v"(l23), "v"(off));
+            pair_store4<!(DBG & 16)>(ev[0], ev[1], ev[2], ev[3], s_out, neg1, rsY, off);
         } else {
             __builtin_amdgcn_raw_buffer_store_b128((u32x4){__float_as_uint(ev[0]), __float_as_uint(ev[1]), __float_as_uint(ev[2]), __float_as_uint(ev[3])}, rsY, off, 0, 0);
         }
@@ -472,14 +461,7 @@ __global__ __launch_bounds__(2048 / NRW, 1) void conv3x3_direct_p_kernel(ConvDir
 
     if (p.amax_out) {
         __syncthreads();
-        unsigned *s_amax = (unsigned *)dp_smem;
-        if (tid == 0) *s_amax = 0u;
-        __syncthreads();
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) my_amax = fmaxf(my_amax, __shfl_xor(my_amax, o, 64));
-        if (lane == 0) atomicMax(s_amax, __float_as_uint(my_amax));
-        __syncthreads();
-        if (tid == 0 && *s_amax > *(volatile unsigned *)p.amax_out) atomicMax(p.amax_out, *s_amax);
+        amax_publish(my_amax, p.amax_out, dp_smem, tid, lane);
     }
 }
 
@@ -523,55 +505,32 @@ CSLAM_API int cslam_conv3x3_direct_p_dev(const void *d_x, int x_pairs, const uns
     // registers (84 - 236 bytes of scratch: 1.05 ms), and without the epilogue, where it does fit, it is no faster (0.475 against 0.479 ms:
     // profiles/r06_c_dp_ablations.log) -- what separates this kernel from its matrix-only time is not issue slots a second wave could fill
     int nrw = 8;
+    const int rm = !d_res ? 0 : (res_pairs ? 2 : 1);
+    const dim3 g(grid), b4(256);
 #ifdef CSLAM_ABLATIONS
     if (const char *e = getenv("CSLAM_DP_NRW")) nrw = atoi(e) == 4 ? 4 : 8;
-#define DP_NRW4(X) X
-#else
-#define DP_NRW4(X) do { } while (0)
-#endif
-#define DP_LAUNCH_N(R_, O_, N_) do { \
-        static DeviceOnce once; int once_dev; \
-        if (once.todo(&once_dev)) { \
-            HIP_TRY(hipFuncSetAttribute((const void *)conv3x3_direct_p_kernel<R_, O_, N_>, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS(32 / N_))); \
-            once.done(once_dev); } \
-        hipLaunchKernelGGL((conv3x3_direct_p_kernel<R_, O_, N_>), dim3(grid), dim3(2048 / N_), DP_LDS(32 / N_), st, a); } while (0)
-#define DP_LAUNCH(R_, O_) do { if (nrw == 8) DP_LAUNCH_N(R_, O_, 8); else DP_NRW4(DP_LAUNCH_N(R_, O_, 4)); } while (0)
-    const int rm = !d_res ? 0 : (res_pairs ? 2 : 1);
-#ifdef CSLAM_ABLATIONS
+    const dim3 b8(512);
     if (const char *e = getenv("CSLAM_DP_DBG")) {              // timing-only ablations (wrong results): measurement build, pair-format output
         const int d = atoi(e);
-#define DP_LAUNCH_D2(R_, N_, D) do { HIP_TRY(hipFuncSetAttribute((const void *)conv3x3_direct_p_kernel<R_, true, N_, D>, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS(32 / N_))); \
-            hipLaunchKernelGGL((conv3x3_direct_p_kernel<R_, true, N_, D>), dim3(grid), dim3(2048 / N_), DP_LDS(32 / N_), st, a); } while (0)
-#define DP_LAUNCH_D(D) do { if (rm == 2) { if (nrw == 8) DP_LAUNCH_D2(2, 8, D); else DP_LAUNCH_D2(2, 4, D); } \
-                            else { if (nrw == 8) DP_LAUNCH_D2(0, 8, D); else DP_LAUNCH_D2(0, 4, D); } \
-        HIP_TRY(hipGetLastError()); return CSLAM_OK; } while (0)
-        if (d == 1) DP_LAUNCH_D(1);
-        if (d == 2) DP_LAUNCH_D(2);
-        if (d == 4) DP_LAUNCH_D(4);
-        if (d == 7) DP_LAUNCH_D(7);
-        if (d == 16) DP_LAUNCH_D(16);
-        if (d == 23) DP_LAUNCH_D(23);
-#undef DP_LAUNCH_D
-#undef DP_LAUNCH_D2
+        auto dbg = [&](auto d_tag) {                           // <shortcut (pair format or none), pairs out, rows per wave, DBG>
+            constexpr int D = decltype(d_tag)::value;
+            if (rm == 2) return nrw == 8 ? launch_lds<conv3x3_direct_p_kernel<2, true, 8, D>>(g, b4, DP_LDS(4), st, a) : launch_lds<conv3x3_direct_p_kernel<2, true, 4, D>>(g, b8, DP_LDS(8), st, a);
+            return nrw == 8 ? launch_lds<conv3x3_direct_p_kernel<0, true, 8, D>>(g, b4, DP_LDS(4), st, a) : launch_lds<conv3x3_direct_p_kernel<0, true, 4, D>>(g, b8, DP_LDS(8), st, a);
+        };
+        if (d == 1) return dbg(DP_C(1));
+        if (d == 2) return dbg(DP_C(2));
+        if (d == 4) return dbg(DP_C(4));
+        if (d == 7) return dbg(DP_C(7));
+        if (d == 16) return dbg(DP_C(16));
+        if (d == 23) return dbg(DP_C(23));
+    }
+    if (nrw == 4 && x_pairs) {                                 // the eight-wave form
+        if (out_pairs) return rm == 0 ? launch_lds<conv3x3_direct_p_kernel<0, true, 4>>(g, b8, DP_LDS(8), st, a) : rm == 1 ? launch_lds<conv3x3_direct_p_kernel<1, true, 4>>(g, b8, DP_LDS(8), st, a) : launch_lds<conv3x3_direct_p_kernel<2, true, 4>>(g, b8, DP_LDS(8), st, a);
+        return rm == 0 ? launch_lds<conv3x3_direct_p_kernel<0, false, 4>>(g, b8, DP_LDS(8), st, a) : rm == 1 ? launch_lds<conv3x3_direct_p_kernel<1, false, 4>>(g, b8, DP_LDS(8), st, a) : launch_lds<conv3x3_direct_p_kernel<2, false, 4>>(g, b8, DP_LDS(8), st, a);
     }
 #endif
-    if (!x_pairs) {
-#define DP_LAUNCH_X(O_) do { \
-        static DeviceOnce once; int once_dev; \
-        if (once.todo(&once_dev)) { \
-            HIP_TRY(hipFuncSetAttribute((const void *)conv3x3_direct_p_kernel<0, O_, 8, 0, true>, hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS(4))); \
-            once.done(once_dev); } \
-        hipLaunchKernelGGL((conv3x3_direct_p_kernel<0, O_, 8, 0, true>), dim3(grid), dim3(256), DP_LDS(4), st, a); } while (0)
-        if (out_pairs) DP_LAUNCH_X(true); else DP_LAUNCH_X(false);
-#undef DP_LAUNCH_X
-        HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
-    }
-    if (out_pairs) { if (rm == 0) DP_LAUNCH(0, true); else if (rm == 1) DP_LAUNCH(1, true); else DP_LAUNCH(2, true); }
-    else { if (rm == 0) DP_LAUNCH(0, false); else if (rm == 1) DP_LAUNCH(1, false); else DP_LAUNCH(2, false); }
-#undef DP_LAUNCH
-#undef DP_LAUNCH_N
-#undef DP_NRW4
-    HIP_TRY(hipGetLastError());
-    return CSLAM_OK;
+    (void)nrw;
+    if (!x_pairs) return out_pairs ? launch_lds<conv3x3_direct_p_kernel<0, true, 8, 0, true>>(g, b4, DP_LDS(4), st, a) : launch_lds<conv3x3_direct_p_kernel<0, false, 8, 0, true>>(g, b4, DP_LDS(4), st, a);
+    if (out_pairs) return rm == 0 ? launch_lds<conv3x3_direct_p_kernel<0, true, 8>>(g, b4, DP_LDS(4), st, a) : rm == 1 ? launch_lds<conv3x3_direct_p_kernel<1, true, 8>>(g, b4, DP_LDS(4), st, a) : launch_lds<conv3x3_direct_p_kernel<2, true, 8>>(g, b4, DP_LDS(4), st, a);
+    return rm == 0 ? launch_lds<conv3x3_direct_p_kernel<0, false, 8>>(g, b4, DP_LDS(4), st, a) : rm == 1 ? launch_lds<conv3x3_direct_p_kernel<1, false, 8>>(g, b4, DP_LDS(4), st, a) : launch_lds<conv3x3_direct_p_kernel<2, false, 8>>(g, b4, DP_LDS(4), st, a);
 }

@@ -1053,38 +1053,17 @@ static int conv_igemm_launch(const float *d_x, const void *d_w2, const float *d_
         sp.n_xcd = n_cu % 8 == 0 ? 8 : 1;
         int nb = (sp.ntiles + 1) / 2 < n_cu ? (sp.ntiles + 1) / 2 : n_cu;       // a workgroup = two groups of four waves = two tiles at a time
         if (nb >= sp.n_xcd) nb -= nb % sp.n_xcd; else sp.n_xcd = 1;
-        static DeviceOnce once_sp; int once_dev_sp;
-        if (once_sp.todo(&once_dev_sp)) {
-            HIP_TRY(hipFuncSetAttribute((const void *)conv_stem_pool_patch_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, SP_LDS));
-            once_sp.done(once_dev_sp); }
-        hipLaunchKernelGGL(conv_stem_pool_patch_kernel, dim3(nb), dim3(512), SP_LDS, st, sp);
-        HIP_TRY(hipGetLastError());
-        return CSLAM_OK;
+        return launch_lds<conv_stem_pool_patch_kernel>(dim3(nb), dim3(512), SP_LDS, st, sp);
     }
-#define CI_LAUNCH(TM_, TN_, ST_) do { \
-        static DeviceOnce once; int once_dev; \
-        if (once.todo(&once_dev)) { \
-            HIP_TRY(hipFuncSetAttribute((const void *)conv_igemm_h2_kernel<TM_, TN_, ST_>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-            once.done(once_dev); } \
-        hipLaunchKernelGGL((conv_igemm_h2_kernel<TM_, TN_, ST_>), grid, blk, lds, st, a); } while (0)
-#define CI_LAUNCH_K(TM_, TN_, AM_) do { \
-        static DeviceOnce once; int once_dev; \
-        if (once.todo(&once_dev)) { \
-            HIP_TRY(hipFuncSetAttribute((const void *)conv_igemm_h2_kernel<TM_, TN_, AM_, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-            once.done(once_dev); } \
-        hipLaunchKernelGGL((conv_igemm_h2_kernel<TM_, TN_, AM_, true>), grid, blk, lds, st, a); } while (0)
-    if (stem) { if (tn == 128) CI_LAUNCH(128, 128, 1); else CI_LAUNCH(128, 64, 1); }
+    // <TM, TN, activation format, shared rows>
+    if (stem) return tn == 128 ? launch_lds<conv_igemm_h2_kernel<128, 128, 1>>(grid, blk, lds, st, a) : launch_lds<conv_igemm_h2_kernel<128, 64, 1>>(grid, blk, lds, st, a);
 #ifdef CSLAM_ABLATIONS
-    else if (f.x_pairs && kws && big) CI_LAUNCH_K(256, 128, 2);
+    if (f.x_pairs && kws && big) return launch_lds<conv_igemm_h2_kernel<256, 128, 2, true>>(grid, blk, lds, st, a);
 #endif
-    else if (f.x_pairs && kws) { if (tn == 128) CI_LAUNCH_K(128, 128, 2); else CI_LAUNCH_K(128, 64, 2); }
-    else if (kws) { if (tn == 128) CI_LAUNCH_K(128, 128, 0); else CI_LAUNCH_K(128, 64, 0); }
-    else if (f.x_pairs) { if (tn == 128) CI_LAUNCH(128, 128, 2); else CI_LAUNCH(256, 64, 2); }
-    else { if (tn == 128) CI_LAUNCH(128, 128, 0); else CI_LAUNCH(128, 64, 0); }
-#undef CI_LAUNCH
-#undef CI_LAUNCH_K
-    HIP_TRY(hipGetLastError());
-    return CSLAM_OK;
+    if (f.x_pairs && kws) return tn == 128 ? launch_lds<conv_igemm_h2_kernel<128, 128, 2, true>>(grid, blk, lds, st, a) : launch_lds<conv_igemm_h2_kernel<128, 64, 2, true>>(grid, blk, lds, st, a);
+    if (kws) return tn == 128 ? launch_lds<conv_igemm_h2_kernel<128, 128, 0, true>>(grid, blk, lds, st, a) : launch_lds<conv_igemm_h2_kernel<128, 64, 0, true>>(grid, blk, lds, st, a);
+    if (f.x_pairs) return tn == 128 ? launch_lds<conv_igemm_h2_kernel<128, 128, 2>>(grid, blk, lds, st, a) : launch_lds<conv_igemm_h2_kernel<256, 64, 2>>(grid, blk, lds, st, a);
+    return tn == 128 ? launch_lds<conv_igemm_h2_kernel<128, 128, 0>>(grid, blk, lds, st, a) : launch_lds<conv_igemm_h2_kernel<128, 64, 0>>(grid, blk, lds, st, a);
 }
 CSLAM_API int cslam_conv_igemm_h2_dev(const float *d_x, const void *d_w2, const float *d_bias, const float *d_res, int B, int H, int W,
                                       int Cin, int Cout, int KH, int KW, int stride, int pad, int relu, const unsigned *d_amax_in,

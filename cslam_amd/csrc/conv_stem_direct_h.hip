@@ -33,26 +33,17 @@
 #include <hip/hip_fp16.h>
 #include "common.h"
 #include "pairs.h"
+#include "direct_dev.h"
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
 
-#define SD_PP 320                      // bytes per patch pixel: [hi 64 halfs | lo 64 halfs | 64 pad] = 20 sixteen-byte slots, and the 16-byte chunk c
-                                       // (8 channels) of a half sits at chunk c ^ SD_SWZ(pixel column).  Found by search over pitch and
-                                       // swizzle (profiles/r04_v55_*): every ds_read_b128 lane group of a fragment read (8 pixels of K group
-                                       // g, the other 8 of K group g + 1) falls on 16 distinct slots for every column shift, K step and half,
-                                       // and the first layer's ds_write_b64 (16 consecutive pixels, one 8-byte quarter-chunk each) collide
-                                       // 2.5-way on average -- 288 bytes without swizzle: the same reads, 3.75-way writes, 1.1k cycles per block
-#define SD_SWZ(pc) (((pc) >> 1) & 3)
-#define SD_RP (18 * SD_PP)             // 5 760 bytes per patch row
-#define SD_PATCHB (10 * SD_RP)         // 57 600 per buffer
 #define SD_IW 20
 #define SD_IMG (12 * SD_IW * 3)        // dwords of the packed [hi | lo] image patch [12][20][3]
 #define SD_T9 (20 * 17)                // ... and of its third channel once more, column-major [20][17] (rows 12 .. 16: zeros): the ninth tap
 #define SD_IMGB (SD_IMG + SD_T9)       // dwords per image buffer
-#define SD_NPIX 180                    // 10 x 18 patch pixels
-#define SD_LDS (2 * SD_PATCHB + 2 * SD_IMGB * 4)
+#define SD_LDS (2 * DPATCH_BYTES + 2 * SD_IMGB * 4)   // [2] patches (direct_dev.h: the 64-channel pair patch) | [2] image patches
 
 struct StemDirectArgs {
     const float *x0; const unsigned *w1; const float *b1; const float *sumw; float inv_sw1;
@@ -82,7 +73,7 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int gq = lane >> 4, l15 = lane & 15;
     // LDS: [2] patches | [2] image patches
-    unsigned *const s_img_all = (unsigned *)(sd_smem + 2 * SD_PATCHB);
+    unsigned *const s_img_all = (unsigned *)(sd_smem + 2 * DPATCH_BYTES);
 
     // ---- scales
     const float a0 = fminf(fmaxf(__uint_as_float(*p.amax_in), 1e-30f), 1e30f);
@@ -98,17 +89,9 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
     const float sx = ldexpf(1.0f, e_ - 1);
     const float inv2 = p.inv_sw2 / sx;
 
-    // Blocks to workgroups, XCD-aware: workgroup w runs on XCD w % 8 (round-robin dispatch), and every XCD has an L2 of its own.  Each XCD
-    // takes one CONTIGUOUS eighth of the blocks, its workgroups walk it side by side -- the blocks whose image patches overlap (left /
-    // right neighbours, and the row below 14 blocks later) are then read through ONE L2 at about the same time.  (Block b -> workgroup
-    // b % grid: every halo line was fetched by two or three XCDs, 723 MB of L2 misses for a 154 MB image input.)
-    const bool by_xcd = (gridDim.x & 7) == 0;
-    const int wg_xcd = by_xcd ? (int)blockIdx.x & 7 : 0, wg_j = by_xcd ? (int)blockIdx.x >> 3 : (int)blockIdx.x;
-    const int wg_per = by_xcd ? (int)gridDim.x >> 3 : (int)gridDim.x;
-    const int per_xcd = by_xcd ? (p.nblk + 7) >> 3 : p.nblk;
-    const int blk_beg = wg_xcd * per_xcd;
-    const int blk_cnt = min(per_xcd, p.nblk - blk_beg);        // blocks of this XCD's range (may be <= 0 for the last ones of a tiny launch)
-    const int n_mine = blk_cnt > wg_j ? (blk_cnt - wg_j + wg_per - 1) / wg_per : 0;
+    // blocks to workgroups by XCD (direct_dev.h)
+    const DirectPart part = direct_partition(p.nblk);
+    const int n_mine = part.n_mine;
     if (n_mine <= 0) return;
 
     // ---- this wave's operands, register-resident for the whole kernel
@@ -145,17 +128,8 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
         e_dst[j] = e < SD_IMG ? (r * SD_IW + c) * 3 + ci : -1;
         e_rc[j] = (ci << 16) | (r << 8) | c;
     }
-    struct Blk { int img, by, bx; };
-    auto decode_blk = [&](int bi) {
-        int blk = wg_j + bi * wg_per;
-        blk = blk_beg + (blk < blk_cnt ? blk : blk_cnt - 1);
-        const int per_img = p.gxb * p.gyb;
-        Blk b;
-        b.img = blk / per_img;
-        const int rem = blk - b.img * per_img;
-        b.by = rem / p.gxb; b.bx = rem - b.by * p.gxb;
-        return b;
-    };
+    typedef DirectBlk Blk;
+    auto decode_blk = [&](int bi) { return direct_decode_blk(part, bi, p.gxb, p.gyb); };
     float raw[3];
     auto img_load = [&](const Blk &b) {
 #pragma unroll
@@ -187,10 +161,10 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
 #pragma unroll
     for (int t = 0; t < 12; ++t) {
         int pp = 16 * t + l15;
-        pp = pp < SD_NPIX ? pp : SD_NPIX - 1;
+        pp = pp < DPATCH_NPIX ? pp : DPATCH_NPIX - 1;
         const int pr = (pp * 3641) >> 16, pc = pp - 18 * pr;                      // pp / 18 for pp < 4096
         c1_src[t] = (gq < 3 ? ((pr + gq) * SD_IW + pc) * 3 : SD_IMG + (pc + 2) * 17 + pr) * 4;
-        c1_dst[t] = pr * SD_RP + pc * SD_PP + (((2 * wave + (gq >> 1)) ^ SD_SWZ(pc)) << 4) + (gq & 1) * 8;
+        c1_dst[t] = DPATCH_OFF(pr, pc, 2 * wave + (gq >> 1), gq & 1);
     }
     for (int i = tid; i < 2 * 20 * 5; i += 256)                // rows 12 .. 16 of the column-major copies: never written again
         s_img_all[(i / 100) * SD_IMGB + SD_IMG + ((i % 100) / 5) * 17 + 12 + (i % 5)] = 0u;
@@ -254,9 +228,9 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
             const int pp = lane + 64 * k;
             const int pr = (pp * 3641) >> 16, pc = pp - 18 * pr;
             const int gy = gy0 + pr, gx = gx0 + pc;
-            if (pp < SD_NPIX && !((gy >= 0) & (gy < p.H) & (gx >= 0) & (gx < p.W))) {
-                char *d = patch + pr * SD_RP + pc * SD_PP;
-                const int c0 = ((2 * wave) ^ SD_SWZ(pc)) << 4, c1_ = ((2 * wave + 1) ^ SD_SWZ(pc)) << 4;
+            if (pp < DPATCH_NPIX && !((gy >= 0) & (gy < p.H) & (gx >= 0) & (gx < p.W))) {
+                char *d = patch + pr * DPATCH_RP + pc * DPATCH_PP;
+                const int c0 = ((2 * wave) ^ DPATCH_SWZ(pc)) << 4, c1_ = ((2 * wave + 1) ^ DPATCH_SWZ(pc)) << 4;
                 *(uint4 *)(d + c0) = make_uint4(0u, 0u, 0u, 0u); *(uint4 *)(d + c1_) = make_uint4(0u, 0u, 0u, 0u);
                 *(uint4 *)(d + 128 + c0) = make_uint4(0u, 0u, 0u, 0u); *(uint4 *)(d + 128 + c1_) = make_uint4(0u, 0u, 0u, 0u);
             }
@@ -324,13 +298,13 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
     f32x4 acc[8];
     int fr_off[3];                                             // the lane's fragment offset at column shift dx: pixel l15 + dx, chunk gq ^ swizzle
 #pragma unroll
-    for (int dx = 0; dx < 3; ++dx) fr_off[dx] = (l15 + dx) * SD_PP + ((gq ^ SD_SWZ(l15 + dx)) << 4);
+    for (int dx = 0; dx < 3; ++dx) fr_off[dx] = DPATCH_OFF(0, l15 + dx, gq, 0);
     f16x8 fh[3], fl[3];
     auto frag_read = [&](auto col_tag, auto r_tag, const char *patch) {
         constexpr int COL = decltype(col_tag)::value, R = decltype(r_tag)::value;
         constexpr int DX = COL >> 1, KS = COL & 1, SLOT = (R + COL) % 3;
-        fh[SLOT] = *(const f16x8 *)(patch + fr_off[DX] + R * SD_RP + KS * 64);
-        fl[SLOT] = *(const f16x8 *)(patch + fr_off[DX] + R * SD_RP + KS * 64 + 128);
+        fh[SLOT] = *(const f16x8 *)(patch + fr_off[DX] + R * DPATCH_RP + KS * 64);
+        fl[SLOT] = *(const f16x8 *)(patch + fr_off[DX] + R * DPATCH_RP + KS * 64 + 128);
     };
     auto rstep = [&](auto col_tag, auto r_tag, const char *patch, const unsigned *s_img, const Blk &nblk, char *npatch) {
         constexpr int COL = decltype(col_tag)::value, R = decltype(r_tag)::value;
@@ -420,8 +394,8 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
     __syncthreads();
     for (int bi = 0; bi < n_mine; ++bi) {
         const int cur = bi & 1;
-        const char *const patch = sd_smem + cur * SD_PATCHB;
-        char *const npatch = sd_smem + (cur ^ 1) * SD_PATCHB;
+        const char *const patch = sd_smem + cur * DPATCH_BYTES;
+        char *const npatch = sd_smem + (cur ^ 1) * DPATCH_BYTES;
         const unsigned *const s_img_next = s_img_all + (cur ^ 1) * SD_IMGB;    // block bi + 1's image
         const Blk nnb = decode_blk(bi + 2);
         img_load(nnb);                                         // in flight until this block's columns are through
@@ -455,14 +429,7 @@ __global__ __launch_bounds__(256, 1) void conv_stem_direct_h_kernel(StemDirectAr
 
     if (p.amax_out) {
         __syncthreads();
-        unsigned *s_amax = (unsigned *)sd_smem;
-        if (tid == 0) *s_amax = 0u;
-        __syncthreads();
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) my_amax = fmaxf(my_amax, __shfl_xor(my_amax, o, 64));
-        if (lane == 0) atomicMax(s_amax, __float_as_uint(my_amax));
-        __syncthreads();
-        if (tid == 0 && *s_amax > *(volatile unsigned *)p.amax_out) atomicMax(p.amax_out, *s_amax);
+        amax_publish(my_amax, p.amax_out, sd_smem, tid, lane);
     }
 }
 
@@ -492,32 +459,20 @@ CSLAM_API int cslam_conv_stem_direct_h_dev(const float *d_x0, const void *d_w1, 
     ARG_CHECK(n_cu > 0, "no HIP device");
     const int grid = (int)(nblk < n_cu ? nblk : n_cu);
     hipStream_t st = (hipStream_t)stream;
-    constexpr int lds = SD_LDS;
-#define SD_LAUNCH(P) do { \
-        static DeviceOnce once; int once_dev; \
-        if (once.todo(&once_dev)) { \
-            HIP_TRY(hipFuncSetAttribute((const void *)conv_stem_direct_h_kernel<P>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-            once.done(once_dev); } \
-        hipLaunchKernelGGL((conv_stem_direct_h_kernel<P>), dim3(grid), dim3(256), lds, st, a); } while (0)
+    const dim3 g(grid), b(256);
 #ifdef CSLAM_ABLATIONS
     if (const char *e = getenv("CSLAM_SD_DBG")) {              // timing-only ablations (wrong results): measurement build
         const int d = atoi(e);
-#define SD_LAUNCH_D(D) do { HIP_TRY(hipFuncSetAttribute((const void *)conv_stem_direct_h_kernel<true, D>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)); \
-        hipLaunchKernelGGL((conv_stem_direct_h_kernel<true, D>), dim3(grid), dim3(256), lds, st, a); HIP_TRY(hipGetLastError()); return CSLAM_OK; } while (0)
-        if (d == 1) SD_LAUNCH_D(1);
-        if (d == 2) SD_LAUNCH_D(2);
-        if (d == 3) SD_LAUNCH_D(3);
-        if (d == 4) SD_LAUNCH_D(4);
-        if (d == 7) SD_LAUNCH_D(7);
-        if (d == 8) SD_LAUNCH_D(8);
-        if (d == 16) SD_LAUNCH_D(16);
-        if (d == 24) SD_LAUNCH_D(24);
-#undef SD_LAUNCH_D
+        if (d == 1) return launch_lds<conv_stem_direct_h_kernel<true, 1>>(g, b, SD_LDS, st, a);
+        if (d == 2) return launch_lds<conv_stem_direct_h_kernel<true, 2>>(g, b, SD_LDS, st, a);
+        if (d == 3) return launch_lds<conv_stem_direct_h_kernel<true, 3>>(g, b, SD_LDS, st, a);
+        if (d == 4) return launch_lds<conv_stem_direct_h_kernel<true, 4>>(g, b, SD_LDS, st, a);
+        if (d == 7) return launch_lds<conv_stem_direct_h_kernel<true, 7>>(g, b, SD_LDS, st, a);
+        if (d == 8) return launch_lds<conv_stem_direct_h_kernel<true, 8>>(g, b, SD_LDS, st, a);
+        if (d == 16) return launch_lds<conv_stem_direct_h_kernel<true, 16>>(g, b, SD_LDS, st, a);
+        if (d == 24) return launch_lds<conv_stem_direct_h_kernel<true, 24>>(g, b, SD_LDS, st, a);
     }
 #endif
-    if (pool) SD_LAUNCH(true);
-    else SD_LAUNCH(false);
-#undef SD_LAUNCH
-    HIP_TRY(hipGetLastError());
-    return CSLAM_OK;
+    if (pool) return launch_lds<conv_stem_direct_h_kernel<true>>(g, b, SD_LDS, st, a);
+    return launch_lds<conv_stem_direct_h_kernel<false>>(g, b, SD_LDS, st, a);
 }

@@ -36,10 +36,16 @@
 //                          of (cost << 9 | d), the second best by another with the neighbours of the best masked out; for
 //                          the left-right check the right window and the mirrored left strip take the same buffers.  The
 //                          rules are stereo.h's.  No atomics; a keypoint's result depends on nothing else in the batch.
+//   feat_pyr_level_kernel : the scale pyramid (feat_pyr.h): one launch per level, the frame on grid.y; a thread makes 4 consecutive
+//                          bytes of the level image from the 2 x 2 footprints in the level below and stores them as one word,
+//                          and the level's validity map in the same pass when a depth image is given.
+//   feat_pyr_merge_kernel : a thread per output row of a frame: the levels' rows, each cut at its budget, one after another; the
+//                          position is the exclusive sum of the (at most 8) counts of the frame, added up per thread.  No atomics.
 // A batch of n images occupies n workgroups in the selection, so a small batch leaves most of the chip idle there (accepted
 // as for the PnP kernel: DESIGN.md).
 #include "common.h"
 #include "feat.h"
+#include "feat_pyr.h"
 #include "stereo.h"
 #include "feat_args.h"             // FEAT_TILE, FEAT_MAX_PIXELS, StereoParams and the argument checks
 
@@ -510,6 +516,118 @@ __global__ __launch_bounds__(64) void feat_stereo_kernel(const uint8_t *__restri
     pts[3 * row] = p[0]; pts[3 * row + 1] = p[1]; pts[3 * row + 2] = p[2];
 }
 
+// ---- scale pyramid -------------------------------------------------------------------------------------------------
+// A frame becomes `levels` images of the batch: level l of frame c is image l * n + c of the level layout (level-major: a
+// launch of the level kernel reads one contiguous stretch and writes the next; frame-major measured the same times),
+// whose offsets are multiples of FEAT_PYR_RUN so that a thread's run is one aligned word.  The rules are feat_pyr.h's.
+#define FEAT_PYR_RUN 4             // output bytes per thread, stored as one word
+#define FEAT_PYR_BLOCK 256         // threads: a workgroup covers 1024 consecutive bytes of a level image
+
+struct FeatPyrLevelArgs {
+    const uint8_t *src; const int64_t *src_off; const int32_t *src_hw; int src_at;               // source image src_at + c
+    uint8_t *dst; const int64_t *lvl_off; const int32_t *lvl_hw; int levels, level;
+    const float *depth; const int64_t *off; const int32_t *hw; uint8_t *valid;                    // level 0: depth NULL = no maps
+};
+
+// Level `level` of every frame from the level below it (level 0: from the grey batch, which the rule copies).  A thread
+// walks FEAT_PYR_RUN consecutive pixels of the flat level image, across a row end if need be.
+__global__ __launch_bounds__(FEAT_PYR_BLOCK) void feat_pyr_level_kernel(FeatPyrLevelArgs A) {
+    const int c = blockIdx.y, n = gridDim.y;
+    const FeatImage out = feat_image(A.lvl_off, A.lvl_hw, A.level * n + c);
+    const int npix = out.H * out.W;                        // <= 2^30
+    const int64_t first = ((int64_t)blockIdx.x * FEAT_PYR_BLOCK + threadIdx.x) * FEAT_PYR_RUN;
+    if (first >= npix) return;
+    const int p0 = (int)first;
+    const FeatImage in = feat_image(A.src_off, A.src_hw, A.src_at + c);
+    const uint8_t *g = A.src + in.base;
+    const int H0 = A.hw[2 * c], W0 = A.hw[2 * c + 1];
+    const float *depth = A.depth ? A.depth + A.off[c] : nullptr;
+    int y = p0 / out.W, x = p0 % out.W;
+    int r0, r1, b;
+    feat_pyr_tap(y, out.H, in.H, &r0, &r1, &b);
+    int py = depth ? feat_pyr_base_pixel(y, H0, out.H) : 0;
+    uint32_t word = 0, vword = 0;
+#pragma unroll
+    for (int e = 0; e < FEAT_PYR_RUN; ++e) {
+        if (p0 + e >= npix) break;
+        int c0, c1, a;
+        feat_pyr_tap(x, out.W, in.W, &c0, &c1, &a);
+        const int v = feat_pyr_blend(g[(int64_t)r0 * in.W + c0], g[(int64_t)r0 * in.W + c1], g[(int64_t)r1 * in.W + c0],
+                                     g[(int64_t)r1 * in.W + c1], a, b);
+        word |= (uint32_t)v << (8 * e);
+        if (depth && feat_depth_valid(depth[(int64_t)py * W0 + feat_pyr_base_pixel(x, W0, out.W)])) vword |= 1u << (8 * e);
+        if (++x == out.W) {
+            x = 0;
+            ++y;
+            if (y < out.H) {
+                feat_pyr_tap(y, out.H, in.H, &r0, &r1, &b);
+                if (depth) py = feat_pyr_base_pixel(y, H0, out.H);
+            }
+        }
+    }
+    *reinterpret_cast<uint32_t *>(A.dst + out.base + p0) = word;          // the layout pads every image to whole words
+    if (depth) *reinterpret_cast<uint32_t *>(A.valid + out.base + p0) = vword;
+}
+
+struct FeatPyrMergeArgs {
+    const int32_t *lcount, *lkp, *lresp, *lbins; const uint8_t *ldesc; int stride;   // per level image: [n L], [n L, stride, ..]
+    const double *z;                                       // [n L, stride], or NULL: Z from the depth image
+    const float *depth; const int64_t *off; const int32_t *hw, *lvl_hw;
+    const double *cams; int levels, max_features;
+    int budget[FEAT_PYR_MAX_LEVELS];
+    int32_t *count; double *kp; int32_t *level_kp, *level, *base_px, *resp, *bins; uint8_t *desc; double *pts;   // base_px, pts: may be NULL
+};
+
+// Row k of frame c: the levels' rows one after another, level 0 first, each level cut at its budget.  The position of a
+// level's rows is the exclusive sum of the counts before it, which every thread adds up for itself: no atomics.
+__global__ __launch_bounds__(256) void feat_pyr_merge_kernel(FeatPyrMergeArgs A) {
+    const int c = blockIdx.y, frames = gridDim.y, k = blockIdx.x * 256 + threadIdx.x;
+    int at = 0, l = -1, j = 0;
+    for (int e = 0; e < A.levels; ++e) {
+        int n = A.lcount[e * frames + c];
+        n = n < A.budget[e] ? n : A.budget[e];
+        n = n < A.stride ? n : A.stride;
+        if (l < 0 && k < at + n) { l = e; j = k - at; }
+        at += n;
+    }
+    if (k == 0) A.count[c] = at;
+    if (l < 0) return;
+    const int im = l * frames + c;
+    const int64_t src = (int64_t)im * A.stride + j, row = (int64_t)c * A.max_features + k;
+    const int H0 = A.hw[2 * c], W0 = A.hw[2 * c + 1], Hl = A.lvl_hw[2 * im], Wl = A.lvl_hw[2 * im + 1];
+    const int x = A.lkp[2 * src], y = A.lkp[2 * src + 1];
+    const double kx = feat_pyr_base_coord(x, W0, Wl), ky = feat_pyr_base_coord(y, H0, Hl);
+    const int px = feat_pyr_base_pixel(x, W0, Wl), py = feat_pyr_base_pixel(y, H0, Hl);
+    A.kp[2 * row] = kx; A.kp[2 * row + 1] = ky;
+    A.level_kp[2 * row] = x; A.level_kp[2 * row + 1] = y;
+    A.level[row] = l;
+    A.resp[row] = A.lresp[src];
+    A.bins[row] = A.lbins[src];
+    const uint4 *d = reinterpret_cast<const uint4 *>(A.ldesc + FEAT_DESC_BYTES * src);
+    uint4 *o = reinterpret_cast<uint4 *>(A.desc + FEAT_DESC_BYTES * row);
+    o[0] = d[0]; o[1] = d[1];
+    if (A.base_px) { A.base_px[2 * row] = px; A.base_px[2 * row + 1] = py; }
+    if (A.pts) {
+        double Z = NAN, p[3];
+        if (A.z) Z = A.z[src];
+        else { const float dz = A.depth[A.off[c] + (int64_t)py * W0 + px]; if (feat_depth_valid(dz)) Z = (double)dz; }
+        feat_pyr_point(kx, ky, Z, A.cams[4 * c], A.cams[4 * c + 1], A.cams[4 * c + 2], A.cams[4 * c + 3], p);
+        A.pts[3 * row] = p[0]; A.pts[3 * row + 1] = p[1]; A.pts[3 * row + 2] = p[2];
+    }
+}
+
+// The merge's point rule on the Z the stereo kernel left in the rows (cams: five numbers per frame): X and Y move from the
+// integer pixel the stereo rule ran at to the keypoint's level-0 coordinates; a rejected keypoint keeps its NaN row.
+__global__ __launch_bounds__(256) void feat_pyr_repoint_kernel(const double *__restrict__ kp, const int32_t *__restrict__ count,
+                                                               const double *__restrict__ cams, int max_features, double *__restrict__ pts) {
+    const int c = blockIdx.y, k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= count[c]) return;
+    const int64_t row = (int64_t)c * max_features + k;
+    double p[3];
+    feat_pyr_point(kp[2 * row], kp[2 * row + 1], pts[3 * row + 2], cams[5 * c], cams[5 * c + 1], cams[5 * c + 2], cams[5 * c + 3], p);
+    pts[3 * row] = p[0]; pts[3 * row + 1] = p[1]; pts[3 * row + 2] = p[2];
+}
+
 // ---- host side -----------------------------------------------------------------------------------------------------
 static StreamScratch g_feat_scratch;
 
@@ -755,6 +873,244 @@ CSLAM_API int cslam_feat_extract_stereo_dev(const uint8_t *d_left, const int64_t
     FeatKeypoints K = {d_kp, nullptr, d_count, max_features};
     feat_launch_describe(gray_l, d_off, d_hw, n, K, max_features, d_bins, d_desc, st);
     feat_launch_stereo(gray_l, gray_r, d_off, d_hw, n, K, max_features, d_cameras, P, d_disparity, d_status, nullptr, d_points, st);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+// ---- scale pyramid: host side --------------------------------------------------------------------------------------
+// The level layout of a batch, from the host sizes: image l * n + c = level l of frame c, every offset a multiple of
+// FEAT_PYR_RUN.  The caller passes the same layout on the device and on the host, as it passes d_off and h_off.
+struct FeatPyrLayout {
+    std::vector<int64_t> off;
+    std::vector<int32_t> hw;
+    FeatShape sh;                                          // of the n * levels level images
+    int budget[FEAT_PYR_MAX_LEVELS];
+};
+
+static int feat_pyr_layout(const int32_t *h_hw, int n, int levels, int min_side, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
+                           FeatPyrLayout *P) {
+    ARG_CHECK(levels >= 1 && levels <= FEAT_PYR_MAX_LEVELS, "levels must be in [1, 8]");
+    ARG_CHECK((int64_t)n * levels <= 65535, "n * levels must be at most 65535");
+    ARG_CHECK(h_lvl_off != nullptr && h_lvl_hw != nullptr, "h_lvl_off and h_lvl_hw are required");
+    P->off.assign((size_t)n * levels + 1, 0);
+    P->hw.assign((size_t)n * levels * 2, 0);
+    P->sh.px.largest = 0;
+    P->sh.px.smallest = INT64_MAX;
+    P->sh.max_h = P->sh.max_w = 0;
+    for (int l = 0; l < levels; ++l)
+        for (int c = 0; c < n; ++c) {
+            const int H = h_hw[2 * c], W = h_hw[2 * c + 1];
+            ARG_CHECK(H <= FEAT_PYR_MAX_SIDE && W <= FEAT_PYR_MAX_SIDE, "a pyramid image has at most 2^20 rows and columns");
+            const int i = l * n + c, Hl = feat_pyr_size(H, l), Wl = feat_pyr_size(W, l);
+            ARG_CHECK(Hl >= min_side && Wl >= min_side, "a frame is too small for its top level (every level: at least 2 x 2, and 2 * border + 1 on each side)");
+            const int64_t px = (int64_t)Hl * Wl;
+            P->hw[2 * i] = Hl;
+            P->hw[2 * i + 1] = Wl;
+            P->off[i + 1] = P->off[i] + round_up64(px, FEAT_PYR_RUN);
+            if (px > P->sh.px.largest) P->sh.px.largest = px;
+            if (px < P->sh.px.smallest) P->sh.px.smallest = px;
+            if (Hl > P->sh.max_h) P->sh.max_h = Hl;
+            if (Wl > P->sh.max_w) P->sh.max_w = Wl;
+        }
+    P->sh.px.total = P->off[(size_t)n * levels];
+    for (size_t i = 0; i < P->off.size(); ++i) ARG_CHECK(h_lvl_off[i] == P->off[i], "h_lvl_off is not the level layout of h_hw");
+    for (size_t i = 0; i < P->hw.size(); ++i) ARG_CHECK(h_lvl_hw[i] == P->hw[i], "h_lvl_hw is not the level layout of h_hw");
+    return CSLAM_OK;
+}
+
+// level 0 from the grey batch, every further level from the one below; the maps in the same passes when depth is given
+static void feat_launch_pyramid(const uint8_t *gray, const int64_t *off, const int32_t *hw, int n, int levels, const float *depth,
+                                const int64_t *lvl_off, const int32_t *lvl_hw, const FeatPyrLayout &P, uint8_t *lvl_gray, uint8_t *lvl_valid,
+                                hipStream_t st) {
+    for (int l = 0; l < levels; ++l) {
+        int64_t largest = 0;
+        for (int c = 0; c < n; ++c) {
+            const int64_t px = (int64_t)P.hw[2 * (l * n + c)] * P.hw[2 * (l * n + c) + 1];
+            if (px > largest) largest = px;
+        }
+        FeatPyrLevelArgs a = {l ? lvl_gray : gray, l ? lvl_off : off, l ? lvl_hw : hw, l ? (l - 1) * n : 0,
+                              lvl_gray, lvl_off, lvl_hw, levels, l, depth, off, hw, lvl_valid};
+        hipLaunchKernelGGL(feat_pyr_level_kernel, dim3((unsigned)ceil_div64(largest, FEAT_PYR_BLOCK * FEAT_PYR_RUN), (unsigned)n),
+                           dim3(FEAT_PYR_BLOCK), 0, st, a);
+    }
+}
+
+static void feat_launch_merge(FeatPyrMergeArgs &a, const FeatPyrLayout &P, int n, hipStream_t st) {
+    for (int l = 0; l < FEAT_PYR_MAX_LEVELS; ++l) a.budget[l] = l < a.levels ? P.budget[l] : 0;
+    hipLaunchKernelGGL(feat_pyr_merge_kernel, dim3((unsigned)ceil_div64(a.max_features, 256), (unsigned)n), dim3(256), 0, st, a);
+}
+
+CSLAM_API int cslam_feat_pyramid_dev(const uint8_t *d_gray, const int64_t *d_off, const int32_t *d_hw, int n, int levels,
+                                     const float *d_depth, const int64_t *d_lvl_off, const int32_t *d_lvl_hw, uint8_t *d_lvl_gray,
+                                     uint8_t *d_lvl_valid, const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off,
+                                     const int32_t *h_lvl_hw, void *stream) {
+    FeatShape sh;
+    FeatPyrLayout P;
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_pyr_layout(h_hw, n, levels, 2, h_lvl_off, h_lvl_hw, &P))) return rc;
+    ARG_CHECK(d_gray && d_off && d_hw && d_lvl_off && d_lvl_hw && d_lvl_gray, "NULL argument");
+    ARG_CHECK((d_depth != nullptr) == (d_lvl_valid != nullptr), "d_lvl_valid goes with d_depth");
+    ARG_CHECK((uintptr_t)d_lvl_gray % FEAT_PYR_RUN == 0 && (uintptr_t)d_lvl_valid % FEAT_PYR_RUN == 0, "the level images start on a 4-byte boundary");
+    PTR_DEVICE(d_gray);
+    feat_launch_pyramid(d_gray, d_off, d_hw, n, levels, d_depth, d_lvl_off, d_lvl_hw, P, d_lvl_gray, d_lvl_valid, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_pyramid_merge_dev(const int32_t *d_lvl_count, const int32_t *d_lvl_kp, const int32_t *d_lvl_resp,
+                                           const int32_t *d_lvl_bins, const uint8_t *d_lvl_desc, const double *d_lvl_z, int stride,
+                                           const int32_t *d_hw, const int32_t *d_lvl_hw, const double *d_cameras, int n, int levels,
+                                           int max_features, int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels,
+                                           int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc, double *d_points, const int32_t *h_hw,
+                                           const int64_t *h_lvl_off, const int32_t *h_lvl_hw, void *stream) {
+    FeatPyrLayout P;
+    BATCH_COUNT_CHECK(n);
+    ARG_CHECK(h_hw != nullptr, "h_hw is required");
+    for (int c = 0; c < n; ++c) ARG_CHECK(h_hw[2 * c] >= 2 && h_hw[2 * c + 1] >= 2, "an image is at least 2 x 2");
+    int rc = feat_pyr_layout(h_hw, n, levels, 2, h_lvl_off, h_lvl_hw, &P);
+    if (rc) return rc;
+    ARG_CHECK(max_features >= 1 && max_features <= 65535, "max_features must be in [1, 65535]");
+    ARG_CHECK(stride >= 1 && stride <= 65535, "stride must be in [1, 65535]");
+    ARG_CHECK(d_lvl_count && d_lvl_kp && d_lvl_resp && d_lvl_bins && d_lvl_desc && d_lvl_z && d_hw && d_lvl_hw && d_cameras && d_count && d_kp &&
+                  d_level_kp && d_levels && d_resp && d_bins && d_desc && d_points,
+              "NULL argument");
+    ARG_CHECK((uintptr_t)d_lvl_desc % 16 == 0 && (uintptr_t)d_desc % 16 == 0, "the descriptors start on a 16-byte boundary");
+    PTR_DEVICE(d_lvl_kp);
+    feat_pyr_budgets(max_features, levels, P.budget);
+    FeatPyrMergeArgs a = {d_lvl_count, d_lvl_kp, d_lvl_resp, d_lvl_bins, d_lvl_desc, stride, d_lvl_z, nullptr, nullptr, d_hw, d_lvl_hw,
+                          d_cameras, levels, max_features, {0}, d_count, d_kp, d_level_kp, d_levels, nullptr, d_resp, d_bins, d_desc, d_points};
+    feat_launch_merge(a, P, n, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+// what both pyramid chains share up to the per-level rows: level images (and maps), response, selection with the largest
+// budget (a level's first rows are its selection at any smaller one), bins and descriptors on the level images
+struct FeatPyrRows { uint8_t *gray; int32_t *count, *kp, *resp, *bins; uint8_t *desc; int stride; };
+
+static int feat_pyr_rows(const uint8_t *gray0, const float *mask_depth, const int64_t *d_off, const int32_t *d_hw, int n, int levels,
+                         const int64_t *d_lvl_off, const int32_t *d_lvl_hw, const FeatPyrLayout &P, double quality, int min_distance,
+                         int border, uint8_t *lvl_valid, int32_t *R, int32_t *rmax, const FeatSelScratch &s, const FeatPyrRows &rows,
+                         hipStream_t st) {
+    const int nl = n * levels;
+    feat_launch_pyramid(gray0, d_off, d_hw, n, levels, mask_depth, d_lvl_off, d_lvl_hw, P, rows.gray, lvl_valid, st);
+    int rc = feat_launch_response(rows.gray, d_lvl_off, d_lvl_hw, nl, P.sh, R, rmax, st);
+    if (rc) return rc;
+    feat_launch_select(R, rmax, mask_depth ? lvl_valid : nullptr, nullptr, d_lvl_off, d_lvl_hw, nl, P.sh, quality, min_distance, border,
+                       rows.stride, s, rows.count, rows.kp, rows.resp, st);
+    FeatKeypoints K = {rows.kp, nullptr, rows.count, rows.stride};
+    feat_launch_describe(rows.gray, d_lvl_off, d_lvl_hw, nl, K, rows.stride, rows.bins, rows.desc, st);
+    return CSLAM_OK;
+}
+
+static void feat_pyr_rows_carve(Carver &cv, const FeatPyrLayout &P, int nl, bool maps, uint8_t **lvl_valid, int32_t **R, int32_t **rmax,
+                                FeatSelScratch *s, FeatPyrRows *rows) {
+    const size_t total = (size_t)P.sh.px.total, r = (size_t)nl * rows->stride;
+    rows->gray = cv.take<uint8_t>(total);
+    *lvl_valid = maps ? cv.take<uint8_t>(total) : nullptr;
+    *R = cv.take<int32_t>(total);
+    *rmax = cv.take<int32_t>((size_t)nl);
+    feat_sel_carve(cv, total, s);
+    rows->count = cv.take<int32_t>((size_t)nl);
+    rows->kp = cv.take<int32_t>(2 * r);
+    rows->resp = cv.take<int32_t>(r);
+    rows->bins = cv.take<int32_t>(r);
+    rows->desc = cv.take<uint8_t>(FEAT_DESC_BYTES * r);
+}
+
+CSLAM_API int cslam_feat_extract_pyramid_dev(const uint8_t *d_src, const int64_t *d_src_off, const float *d_depth, const int64_t *d_off,
+                                             const int32_t *d_hw, const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
+                                             const int32_t *d_lvl_hw, double quality_level, int min_distance, int border, int max_features,
+                                             int depth_as_mask, int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels,
+                                             int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc, double *d_points, const int64_t *h_src_off,
+                                             const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
+                                             void *stream) {
+    FeatShape sh;
+    FeatPyrLayout P;
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_src_check(h_src_off, h_off, n))) return rc;
+    if ((rc = feat_select_checks(quality_level, min_distance, border, max_features))) return rc;
+    if ((rc = feat_pyr_layout(h_hw, n, levels, 2 * border + 1, h_lvl_off, h_lvl_hw, &P))) return rc;
+    ARG_CHECK(d_src && d_src_off && d_depth && d_off && d_hw && d_cameras && d_lvl_off && d_lvl_hw && d_count && d_kp && d_level_kp && d_levels &&
+                  d_resp && d_bins && d_desc && d_points,
+              "NULL argument");
+    ARG_CHECK((uintptr_t)d_desc % 16 == 0, "the descriptors start on a 16-byte boundary");
+    PTR_DEVICE(d_src);
+    hipStream_t st = (hipStream_t)stream;
+    feat_pyr_budgets(max_features, levels, P.budget);
+    FeatSelScratch s;
+    FeatPyrRows rows = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, P.budget[0]};
+    uint8_t *gray, *lvl_valid;
+    int32_t *R, *rmax;
+    auto layout = [&](Carver &cv) {
+        gray = cv.take<uint8_t>((size_t)sh.px.total);
+        feat_pyr_rows_carve(cv, P, n * levels, depth_as_mask != 0, &lvl_valid, &R, &rmax, &s, &rows);
+    };
+    SCRATCH_CARVE(g_feat_scratch, st, (size_t)1 << 20, layout);
+    feat_launch_gray(d_src, d_src_off, d_off, n, sh, gray, st);
+    if ((rc = feat_pyr_rows(gray, depth_as_mask ? d_depth : nullptr, d_off, d_hw, n, levels, d_lvl_off, d_lvl_hw, P, quality_level, min_distance,
+                            border, lvl_valid, R, rmax, s, rows, st)))
+        return rc;
+    FeatPyrMergeArgs a = {rows.count, rows.kp, rows.resp, rows.bins, rows.desc, rows.stride, nullptr, d_depth, d_off, d_hw, d_lvl_hw,
+                          d_cameras, levels, max_features, {0}, d_count, d_kp, d_level_kp, d_levels, nullptr, d_resp, d_bins, d_desc, d_points};
+    feat_launch_merge(a, P, n, st);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_extract_stereo_pyramid_dev(const uint8_t *d_left, const int64_t *d_left_off, const uint8_t *d_right,
+                                                    const int64_t *d_right_off, const int64_t *d_off, const int32_t *d_hw,
+                                                    const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
+                                                    const int32_t *d_lvl_hw, double quality_level, int min_distance, int border,
+                                                    int max_features, int min_disparity, int max_disparity, int uniqueness, int lr_tolerance,
+                                                    int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels, int32_t *d_resp,
+                                                    int32_t *d_bins, uint8_t *d_desc, double *d_points, double *d_disparity, int32_t *d_status,
+                                                    const int64_t *h_left_off, const int64_t *h_right_off, const int64_t *h_off,
+                                                    const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
+                                                    const double *h_cameras, void *stream) {
+    FeatShape sh;
+    FeatPyrLayout P;
+    const StereoParams SP = {min_disparity, max_disparity, uniqueness, lr_tolerance};
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_src_check(h_left_off, h_off, n))) return rc;
+    if ((rc = feat_src_check(h_right_off, h_off, n))) return rc;
+    if ((rc = feat_select_checks(quality_level, min_distance, border, max_features))) return rc;
+    if ((rc = feat_stereo_checks(SP, h_cameras, n))) return rc;
+    if ((rc = feat_pyr_layout(h_hw, n, levels, 2 * border + 1, h_lvl_off, h_lvl_hw, &P))) return rc;
+    ARG_CHECK(d_left && d_left_off && d_right && d_right_off && d_off && d_hw && d_cameras && d_lvl_off && d_lvl_hw && d_count && d_kp &&
+                  d_level_kp && d_levels && d_resp && d_bins && d_desc && d_points && d_disparity && d_status,
+              "NULL argument");
+    ARG_CHECK((uintptr_t)d_desc % 16 == 0, "the descriptors start on a 16-byte boundary");
+    PTR_DEVICE(d_left);
+    hipStream_t st = (hipStream_t)stream;
+    feat_pyr_budgets(max_features, levels, P.budget);
+    FeatSelScratch s;
+    FeatPyrRows rows = {nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, P.budget[0]};
+    uint8_t *gray_l, *gray_r, *lvl_valid;
+    int32_t *R, *rmax, *base_px;
+    auto layout = [&](Carver &cv) {
+        gray_l = cv.take<uint8_t>((size_t)sh.px.total);
+        gray_r = cv.take<uint8_t>((size_t)sh.px.total);
+        base_px = cv.take<int32_t>((size_t)n * max_features * 2);
+        feat_pyr_rows_carve(cv, P, n * levels, false, &lvl_valid, &R, &rmax, &s, &rows);
+    };
+    SCRATCH_CARVE(g_feat_scratch, st, (size_t)1 << 20, layout);
+    feat_launch_gray(d_left, d_left_off, d_off, n, sh, gray_l, st);
+    feat_launch_gray(d_right, d_right_off, d_off, n, sh, gray_r, st);
+    if ((rc = feat_pyr_rows(gray_l, nullptr, d_off, d_hw, n, levels, d_lvl_off, d_lvl_hw, P, quality_level, min_distance, border, lvl_valid, R,
+                            rmax, s, rows, st)))
+        return rc;
+    FeatPyrMergeArgs a = {rows.count, rows.kp, rows.resp, rows.bins, rows.desc, rows.stride, nullptr, nullptr, d_off, d_hw, d_lvl_hw,
+                          d_cameras, levels, max_features, {0}, d_count, d_kp, d_level_kp, d_levels, base_px, d_resp, d_bins, d_desc, nullptr};
+    feat_launch_merge(a, P, n, st);
+    // the stereo rule at the level-0 pixels under the keypoints, then X and Y of its rows at the keypoints' own coordinates
+    FeatKeypoints K = {base_px, nullptr, d_count, max_features};
+    feat_launch_stereo(gray_l, gray_r, d_off, d_hw, n, K, max_features, d_cameras, SP, d_disparity, d_status, nullptr, d_points, st);
+    hipLaunchKernelGGL(feat_pyr_repoint_kernel, dim3((unsigned)ceil_div64(max_features, 256), (unsigned)n), dim3(256), 0, st, d_kp, d_count,
+                       d_cameras, max_features, d_points);
     HIP_TRY(hipGetLastError());
     return CSLAM_OK;
 }

@@ -11,8 +11,8 @@ in integer numpy, and the two agree bit for bit.  Matching only needs every robo
 Images are uint8 [H, W] or [H, W, 3] (B, G, R); depths float32 metres [H, W] (uint16 millimetres are converted on the
 host as np.float32(d) * np.float32(0.001)); a depth is valid iff finite and > 0.  A keypoint is (x, y), x to the right.
 
-Out of scope: depth images smaller than the colour image, scale pyramids, sub-pixel refinement.  A stereo frame (depth
-from the disparity at the keypoints) is visual_stereo.py's.
+Out of scope: depth images smaller than the colour image, sub-pixel refinement.  A stereo frame (depth from the disparity
+at the keypoints) is visual_stereo.py's, the scale pyramid of either visual_pyramid.py's.
 
 There is no CPU path: without the library or a GPU the functions raise CslamHipError.
 """

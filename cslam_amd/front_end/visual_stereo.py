@@ -11,8 +11,8 @@ tests/stereo_reference.py restates, and the two agree bit for bit.
 Images are uint8, the two sides of a frame of the same H x W; a camera is (fx, fy, cx, cy, baseline), baseline in metres,
 one for all frames or one per frame.  Status: 0 accepted, 1 outside, 2 no range, 3 edge, 4 not unique, 5 left-right.
 
-Out of scope: unrectified pairs, different principal points, pyramids, rtabmap's optical-flow variant, Vis/MinDepth and
-Vis/MaxDepth.
+Out of scope: unrectified pairs, different principal points, a pyramid inside the correspondence search (the keypoints' scale
+pyramid is visual_pyramid.py's), rtabmap's optical-flow variant, Vis/MinDepth and Vis/MaxDepth.
 
 There is no CPU path: without the library or a GPU the functions raise CslamHipError.
 """

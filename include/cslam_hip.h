@@ -753,7 +753,8 @@ int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d_points_fr
  *   k / 8 quarter turns (x, y) -> (-y, x).  Bit i = blur(p_i) < blur(q_i), bit i mod 8 of byte i / 8.
  * Points (generateKeypoints3D): depth float32 metres of the image's size, valid iff finite and > 0; in float64
  *   X = ((u - cx) d) / fx, Y = ((v - cy) d) / fy, Z = d; a keypoint without valid depth gives a NaN row.
- * Out of scope: depth images smaller than the colour image, scale pyramids, sub-pixel refinement. */
+ * Out of scope: depth images smaller than the colour image, sub-pixel refinement.  Scale pyramids: the section after the
+ *   stereo keyframes. */
 /* cslam_feat_gray_dev -- the grey conversion of rgbd_handler.cpp:266-312.  d_src uint8, image c = the bytes
  *   [d_src_off[c], d_src_off[c + 1]): H W of them (one channel) or 3 H W (B, G, R interleaved).  d_gray uint8 [total pixels]. */
 int cslam_feat_gray_dev(const uint8_t *d_src, const int64_t *d_src_off, const int64_t *d_off, const int32_t *d_hw, int n,
@@ -824,7 +825,8 @@ int cslam_feat_extract_dev(const uint8_t *d_src, const int64_t *d_src_off, const
  * Point (status 0, otherwise a NaN row): Z = (baseline fx) / disparity, X = ((u - cx) Z) / fx, Y = ((v - cy) Z) / fy.
  * Diagnostic: best int32 [rows, 4] = (d*, a, b, c); d* = -1 for status 1 and 2; each of a, b, c is -1 where that disparity
  *   lies outside [D_lo, D_hi].
- * Out of scope: unrectified pairs, different principal points in the two images, pyramids, rtabmap's optical-flow variant
+ * Out of scope: unrectified pairs, different principal points in the two images, a pyramid inside the correspondence search
+ *   (the keypoints' scale pyramid: the next section), rtabmap's optical-flow variant
  *   of the correspondence search, Vis/MinDepth and Vis/MaxDepth. */
 /* cslam_feat_stereo_dev -- the depth of generateKeypoints3D (rgbd_handler.cpp:309) for a stereo frame
  *   (stereo_handler.cpp:148-227): d_left, d_right uint8 [total pixels] grey in the ragged layout of the feature section
@@ -848,6 +850,85 @@ int cslam_feat_extract_stereo_dev(const uint8_t *d_left, const int64_t *d_left_o
                                   double *d_points, double *d_disparity, int32_t *d_status, const int64_t *h_left_off,
                                   const int64_t *h_right_off, const int64_t *h_off, const int32_t *h_hw, const double *h_cameras,
                                   void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Scale pyramid of the visual keyframes (feat_pyr_level_kernel, feat_pyr_merge_kernel in csrc/feat.hip, the rules in
+ * csrc/feat_pyr.h).  compute_local_descriptors (rgbd_handler.cpp:266-312) detects and describes over rtabmap's ORB scale
+ * pyramid; the sections above do so at one scale, which cannot verify a loop closure seen from another distance.  Here a
+ * frame becomes L images, each an image of its own to the kernels above, and their rows are merged.  Parity with OpenCV's
+ * ORB pyramid is unpinned like the rest of the features.  What is pinned is the rule stated here: integer arithmetic up to
+ * the final coordinates (one float64 division and one subtraction), so the GPU, csrc/feat_pyr.h on the host and
+ * tests/feat_pyramid_reference.py agree bit for bit.  Existing entry points keep their behaviour; levels = 1 gives the rows
+ * of cslam_feat_extract_dev.
+ *
+ * Levels: L = levels in [1, 8], the scale per level 6 / 5.  Level l of an n-pixel axis has n_l = (n 5^l + 6^l / 2) / 6^l
+ *   pixels by integer division.  Every level is at least 2 x 2, and for the extraction at least 2 border + 1 on each side;
+ *   H, W <= 2^20; n L <= 65535.
+ * Resampling: level l from level l - 1 (level 0 is the grey image).  Per axis, for output index x:
+ *   u = ((2 x + 1) n_prev 1024) / (2 n_l) - 512 by floor division in int64, clamped to [0, (n_prev - 1) 1024]; i0 = u >> 10,
+ *   a = u & 1023, i1 = min(i0 + 1, n_prev - 1); likewise (j0, j1, b) for the row.  Pixel = ((g[j0, i0] (1024 - a) + g[j0, i1] a)
+ *   (1024 - b) + (g[j1, i0] (1024 - a) + g[j1, i1] a) b + 2^19) >> 20, which never leaves 0 .. 255.
+ * Level 0 under a level pixel: (x, y) of level l lies over the level-0 pixel px = ((2 x + 1) W) / (2 W_l), py likewise,
+ *   always inside the image.  With a depth image the validity map of level l is 1 where depth[py, px] is valid (finite
+ *   and > 0); it is what the candidate rule above takes as its mask on that level.
+ * Detection and description: per level, in level pixels: its own Rmax, the same quality_level, min_distance and border;
+ *   orientation and descriptor on the level image.
+ * Budget: w_l = 5^l 6^(L - 1 - l); level l gives at most max_features w_l / sum w rows by integer division, level 0 the
+ *   remainder as well (1000 over 4 levels: 323, 268, 223, 186).  Budget a level does not use is not passed on.
+ * Rows of a frame: level 0 first, then level 1, ...; within a level in selection order.  Keypoint in level-0 coordinates,
+ *   float64: kx = (double)((2 x + 1) W) / (double)(2 W_l) - 0.5, ky likewise; at level 0 exactly x.  Point: Z =
+ *   (double)depth[py, px], X = ((kx - cx) Z) / fx, Y = ((ky - cy) Z) / fy; an invalid Z gives a NaN row.
+ * Layout of the level images: image l n + c = level l of frame c (level-major: the images of a level lie one
+ *   after another); d_lvl_hw int32 [n L, 2]; d_lvl_off int64 [n L + 1] PIXEL
+ *   offsets in which every image takes its H_l W_l pixels rounded up to a multiple of 4 (a thread of the level kernel
+ *   stores 4 pixels as one word).  h_lvl_off / h_lvl_hw: the same on the host, required, and checked against h_hw.
+ * Out of scope: a scale-aware match rule, per-level reprojection thresholds in PnP, sub-pixel refinement, dense stereo. */
+/* cslam_feat_pyramid_dev -- the level images of the pyramid under compute_local_descriptors (rgbd_handler.cpp:266-312):
+ *   d_gray uint8 in the ragged layout of the feature section -> d_lvl_gray uint8 [d_lvl_off[n L]] in the level layout.
+ *   d_depth NULL, or float32 [total pixels] together with d_lvl_valid uint8 in the level layout: the validity maps, written
+ *   in the same passes.  d_lvl_gray and d_lvl_valid start on 4-byte boundaries.  One launch per level, no host wait. */
+int cslam_feat_pyramid_dev(const uint8_t *d_gray, const int64_t *d_off, const int32_t *d_hw, int n, int levels, const float *d_depth,
+                           const int64_t *d_lvl_off, const int32_t *d_lvl_hw, uint8_t *d_lvl_gray, uint8_t *d_lvl_valid,
+                           const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw, void *stream);
+/* cslam_feat_pyramid_merge_dev -- the per-level keypoints of compute_local_descriptors (rgbd_handler.cpp:266-312) gathered
+ *   into the rows of a frame.  Per level image i = l n + c: d_lvl_count int32 [n L], d_lvl_kp int32 [n L, stride, 2] in level
+ *   pixels, d_lvl_resp and d_lvl_bins int32 [n L, stride], d_lvl_desc uint8 [n L, stride, 32], d_lvl_z float64 [n L, stride]
+ *   = the Z of each keypoint (not finite or <= 0: a NaN point); the first min(d_lvl_count[i], budget of l, stride) rows of an
+ *   image are taken.  d_cameras float64 [n, 4].  Outputs: d_count int32 [n], d_kp float64 [n, max_features, 2] level-0
+ *   coordinates, d_level_kp int32 [n, max_features, 2], d_levels, d_resp, d_bins int32 [n, max_features], d_desc uint8
+ *   [n, max_features, 32], d_points float64 [n, max_features, 3].  Descriptor arrays start on 16-byte boundaries.  No
+ *   atomics: a row's position is the exclusive sum of the L counts of its frame. */
+int cslam_feat_pyramid_merge_dev(const int32_t *d_lvl_count, const int32_t *d_lvl_kp, const int32_t *d_lvl_resp, const int32_t *d_lvl_bins,
+                                 const uint8_t *d_lvl_desc, const double *d_lvl_z, int stride, const int32_t *d_hw,
+                                 const int32_t *d_lvl_hw, const double *d_cameras, int n, int levels, int max_features, int32_t *d_count,
+                                 double *d_kp, int32_t *d_level_kp, int32_t *d_levels, int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc,
+                                 double *d_points, const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw, void *stream);
+/* cslam_feat_extract_pyramid_dev -- the whole of compute_local_descriptors (rgbd_handler.cpp:266-312) over the pyramid on
+ *   one stream with no host wait in between: grey, the level images (with depth_as_mask != 0 also the validity maps),
+ *   response, selection, bins and descriptors on the n L level images, the merge with Z from d_depth.  Arguments as
+ *   cslam_feat_extract_dev plus the level layout; outputs as cslam_feat_pyramid_merge_dev. */
+int cslam_feat_extract_pyramid_dev(const uint8_t *d_src, const int64_t *d_src_off, const float *d_depth, const int64_t *d_off,
+                                   const int32_t *d_hw, const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
+                                   const int32_t *d_lvl_hw, double quality_level, int min_distance, int border, int max_features,
+                                   int depth_as_mask, int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels,
+                                   int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc, double *d_points, const int64_t *h_src_off,
+                                   const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
+                                   void *stream);
+/* cslam_feat_extract_stereo_pyramid_dev -- compute_local_descriptors for a stereo frame (rgbd_handler.cpp:266-312 with the
+ *   depth of :309 from stereo_handler.cpp:148-227) over the pyramid: the chain above on the left image without a mask; the
+ *   stereo rule runs at the integer level-0 pixel (px, py) under each keypoint on the level-0 greys, and the Z it gives
+ *   goes into the point rule above at (kx, ky); a rejected keypoint keeps its NaN row.  Arguments as
+ *   cslam_feat_extract_stereo_dev plus the level layout; outputs as cslam_feat_pyramid_merge_dev plus d_disparity float64
+ *   and d_status int32 [n, max_features]. */
+int cslam_feat_extract_stereo_pyramid_dev(const uint8_t *d_left, const int64_t *d_left_off, const uint8_t *d_right,
+                                          const int64_t *d_right_off, const int64_t *d_off, const int32_t *d_hw, const double *d_cameras,
+                                          int n, int levels, const int64_t *d_lvl_off, const int32_t *d_lvl_hw, double quality_level,
+                                          int min_distance, int border, int max_features, int min_disparity, int max_disparity,
+                                          int uniqueness, int lr_tolerance, int32_t *d_count, double *d_kp, int32_t *d_level_kp,
+                                          int32_t *d_levels, int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc, double *d_points,
+                                          double *d_disparity, int32_t *d_status, const int64_t *h_left_off, const int64_t *h_right_off,
+                                          const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
+                                          const double *h_cameras, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense stereo: the rule above at every pixel of a rectified pair, and the keyframe cloud made from it

@@ -1,9 +1,11 @@
 """Times of the keyframe features (csrc/feat.hip) by HIP events: one 480 x 640 BGR frame and a batch of 16, each stage
 apart (grey, response, selection, bins and descriptors, points) and the whole chain; then the stereo leg on the same
 frames with a right image 12 columns apart: the stereo kernel alone on the selected keypoints and the chained stereo
-frame.  Prints one JSON line.
+frame.  Then, in the same run, the scale pyramid (front_end/visual_pyramid.py) at 1, 4 and 8 levels on the same frames: the
+chain, the stereo chain, and its stages apart (level images with the validity maps; response, selection with the largest
+level budget, bins and descriptors on the n L level images through the single-scale entries).  Prints one JSON line.
 
-    python tools/perf_visual_features.py [--reps 20]
+    python tools/perf_visual_features.py [--reps 30]
 """
 import argparse
 import json
@@ -28,7 +30,7 @@ def frame(seed, H, W):
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--height", type=int, default=480)
     ap.add_argument("--width", type=int, default=640)
     ap.add_argument("--max-features", type=int, default=1000)
@@ -133,6 +135,73 @@ def main():
                 ms.append(e0.elapsed_time(e1))
             return round(float(np.median(ms)), 4)
 
+        def pyramid(L):
+            """The pyramid chain at L levels and its stages; the staged entries take the level images packed without padding."""
+            from cslam_amd.front_end import visual_pyramid as vp
+            lv = vp._Levels([vp.level_sizes((H, W), L)] * batch, dev)
+            nl, b0 = batch * L, vp.level_budgets(mf, L)[0]
+            hl = (host(lv.off), host(lv.hw))
+            z = lambda shape, dtype: torch.zeros(shape, dtype=dtype, device=dev)
+            p_cnt, p_kp, p_lkp, p_lev = z(batch, torch.int32), z((batch, mf, 2), torch.float64), z((batch, mf, 2), torch.int32), z((batch, mf), torch.int32)
+            t_lg, t_lv = z(lv.total, torch.uint8), z(lv.total, torch.uint8)
+            rows = (p_cnt.data_ptr(), p_kp.data_ptr(), p_lkp.data_ptr(), p_lev.data_ptr(), t_resp.data_ptr(), t_bins.data_ptr(),
+                    t_desc.data_ptr(), t_pts.data_ptr())
+
+            def pyr_chain():
+                _lib.check(lib.cslam_feat_extract_pyramid_dev(t_src.data_ptr(), t_so.data_ptr(), t_depth.data_ptr(), t_off.data_ptr(),
+                                                              t_hw.data_ptr(), t_cam.data_ptr(), batch, L, lv.t_off.data_ptr(), lv.t_hw.data_ptr(),
+                                                              0.001, 7, 19, mf, 1, *rows, host(src_off), *h, *hl, stream()))
+
+            def pyr_stereo_chain():
+                _lib.check(lib.cslam_feat_extract_stereo_pyramid_dev(t_src.data_ptr(), t_so.data_ptr(), t_right.data_ptr(), t_so.data_ptr(),
+                                                                     t_off.data_ptr(), t_hw.data_ptr(), t_scam.data_ptr(), batch, L,
+                                                                     lv.t_off.data_ptr(), lv.t_hw.data_ptr(), 0.001, 7, 19, mf, 1, 128, 15, 1,
+                                                                     *rows, t_disp.data_ptr(), t_status.data_ptr(), host(src_off),
+                                                                     host(src_off), *h, *hl, host(scam), stream()))
+
+            def pyr_levels():
+                _lib.check(lib.cslam_feat_pyramid_dev(t_gray.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch, L, t_depth.data_ptr(),
+                                                      lv.t_off.data_ptr(), lv.t_hw.data_ptr(), t_lg.data_ptr(), t_lv.data_ptr(), *h, *hl,
+                                                      stream()))
+
+            r = {"chain_ms": timed(pyr_chain)}
+            cnt = p_cnt.cpu().numpy()
+            lev = p_lev.cpu().numpy()
+            r["keypoints_per_image"] = round(float(cnt.mean()), 1)
+            r["keypoints_per_level"] = np.round(np.mean([np.bincount(lev[c, :cnt[c]], minlength=L) for c in range(batch)], axis=0), 1).tolist()
+            r["stereo_chain_ms"] = timed(pyr_stereo_chain)
+            gray()
+            r["levels_ms"] = timed(pyr_levels)
+            # the level images and maps packed without padding, for the single-scale entries
+            px = [int(a) * int(b) for a, b in lv.shapes]
+            off_l = offsets(px)
+            pack = lambda t: torch.cat([t[int(lv.off[i]):int(lv.off[i]) + px[i]] for i in range(nl)])
+            q_gray, q_valid, q_off, q_hw = pack(t_lg), pack(t_lv), to_dev(off_l, dev), lv.t_hw
+            q_R, q_max, q_cnt = z(int(off_l[-1]), torch.int32), z(nl, torch.int32), z(nl, torch.int32)
+            q_kp, q_resp, q_bins, q_desc = z((nl, b0, 2), torch.int32), z((nl, b0), torch.int32), z((nl, b0), torch.int32), z((nl, b0, 32), torch.uint8)
+            q_koff = offsets([b0] * nl)
+            q_ko = to_dev(q_koff, dev)
+            hq = (host(off_l), host(lv.hw))
+
+            def pyr_response():
+                _lib.check(lib.cslam_feat_response_dev(q_gray.data_ptr(), q_off.data_ptr(), q_hw.data_ptr(), nl, q_R.data_ptr(), q_max.data_ptr(),
+                                                       *hq, stream()))
+
+            def pyr_select():
+                _lib.check(lib.cslam_feat_select_dev(q_R.data_ptr(), q_max.data_ptr(), q_valid.data_ptr(), q_off.data_ptr(), q_hw.data_ptr(), nl,
+                                                     0.001, 7, 19, b0, q_cnt.data_ptr(), q_kp.data_ptr(), q_resp.data_ptr(), *hq, stream()))
+
+            def pyr_describe():
+                _lib.check(lib.cslam_feat_describe_dev(q_gray.data_ptr(), q_off.data_ptr(), q_hw.data_ptr(), nl, q_kp.data_ptr(), q_ko.data_ptr(),
+                                                       q_bins.data_ptr(), q_desc.data_ptr(), *hq, host(q_koff), stream()))
+
+            r.update({"response_ms": timed(pyr_response), "select_ms": timed(pyr_select)})
+            # the staged describe reads all b0 rows of a level image: rows a level did not fill are moved inside it
+            top = torch.from_numpy(lv.hw[:, ::-1].copy()).to(dev).view(nl, 1, 2) - 19
+            q_kp.copy_(torch.minimum(torch.clamp(q_kp, min=18), top))
+            r["describe_ms"] = timed(pyr_describe)
+            return r
+
         res = {"gray_ms": timed(gray), "response_ms": timed(response), "select_ms": timed(select)}
         cnt = t_cnt.cpu().numpy()
         if not np.all(cnt == mf):                          # the staged describe / points read all mf rows of an image
@@ -146,6 +215,8 @@ def main():
         st = t_status.cpu().numpy()
         res["stereo_keypoints_per_image"] = round(float(n_st.mean()), 1)
         res["stereo_accepted_per_image"] = round(float(np.mean([(st[c, :n_st[c]] == 0).sum() for c in range(batch)])), 1)
+        for L in (1, 4, 8):
+            res["pyramid_%d" % L] = pyramid(L)
         out["batch_%d" % batch] = res
     print(json.dumps(out))
 

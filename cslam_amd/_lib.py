@@ -144,6 +144,10 @@ _SIGNATURES = {
     "cslam_vis_pnp_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _i, _i, C.c_uint64, _vp, _vp, _vp, _vp]),
     "cslam_vis_register_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, C.c_double, _i, _i, _i, C.c_uint64,
                                     _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_vis_pnp_levels_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, _i, _i, C.c_uint64, _vp, _vp, _vp,
+                                      _vp, _vp, _vp]),
+    "cslam_vis_register_levels_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, C.c_double, _i, _i, _i, C.c_uint64,
+                                           _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_vis_hypotheses_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_feat_gray_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cslam_feat_response_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
@@ -162,6 +166,12 @@ _SIGNATURES = {
                                             _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_feat_extract_stereo_pyramid_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _i, _i, _i, _i, _i, _i,
                                                    _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_feat_subpixel_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_feat_extract_pyramid_subpix_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _i, _i, _i, _vp, _vp, _vp,
+                                                   _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_feat_extract_stereo_pyramid_subpix_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, _vp, _vp, C.c_double, _i, _i, _i, _i, _i,
+                                                          _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
+                                                          _vp, _vp, _vp, _vp]),
     "cslam_stereo_dense_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_cloud_keyframes_stereo_dev": (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, C.c_double, C.c_double,
                                               _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

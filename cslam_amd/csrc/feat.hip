@@ -41,6 +41,8 @@
 //                          and the level's validity map in the same pass when a depth image is given.
 //   feat_pyr_merge_kernel : a thread per output row of a frame: the levels' rows, each cut at its budget, one after another; the
 //                          position is the exclusive sum of the (at most 8) counts of the frame, added up per thread.  No atomics.
+//   feat_pyr_subpix_kernel: the sub-pixel offsets (feat_pyr.h): a thread per keypoint reads the response map at it and at its four
+//                          neighbours; the merge then writes the refined level-0 coordinates and takes X and Y from them.
 // A batch of n images occupies n workgroups in the selection, so a small batch leaves most of the chip idle there (accepted
 // as for the PnP kernel: DESIGN.md).
 #include "common.h"
@@ -576,6 +578,7 @@ struct FeatPyrMergeArgs {
     const double *cams; int levels, max_features;
     int budget[FEAT_PYR_MAX_LEVELS];
     int32_t *count; double *kp; int32_t *level_kp, *level, *base_px, *resp, *bins; uint8_t *desc; double *pts;   // base_px, pts: may be NULL
+    const double *loff; double *offs;                      // sub-pixel offsets [n L, stride, 2] -> [n, max_features, 2], or both NULL
 };
 
 // Row k of frame c: the levels' rows one after another, level 0 first, each level cut at its budget.  The position of a
@@ -596,7 +599,13 @@ __global__ __launch_bounds__(256) void feat_pyr_merge_kernel(FeatPyrMergeArgs A)
     const int64_t src = (int64_t)im * A.stride + j, row = (int64_t)c * A.max_features + k;
     const int H0 = A.hw[2 * c], W0 = A.hw[2 * c + 1], Hl = A.lvl_hw[2 * im], Wl = A.lvl_hw[2 * im + 1];
     const int x = A.lkp[2 * src], y = A.lkp[2 * src + 1];
-    const double kx = feat_pyr_base_coord(x, W0, Wl), ky = feat_pyr_base_coord(y, H0, Hl);
+    double kx = feat_pyr_base_coord(x, W0, Wl), ky = feat_pyr_base_coord(y, H0, Hl);
+    if (A.loff) {                                          // the refined coordinates; the pixel under the keypoint stays
+        const double ox = A.loff[2 * src], oy = A.loff[2 * src + 1];
+        kx = feat_pyr_subpix_coord(x, ox, W0, Wl);
+        ky = feat_pyr_subpix_coord(y, oy, H0, Hl);
+        A.offs[2 * row] = ox; A.offs[2 * row + 1] = oy;
+    }
     const int px = feat_pyr_base_pixel(x, W0, Wl), py = feat_pyr_base_pixel(y, H0, Hl);
     A.kp[2 * row] = kx; A.kp[2 * row + 1] = ky;
     A.level_kp[2 * row] = x; A.level_kp[2 * row + 1] = y;
@@ -614,6 +623,19 @@ __global__ __launch_bounds__(256) void feat_pyr_merge_kernel(FeatPyrMergeArgs A)
         feat_pyr_point(kx, ky, Z, A.cams[4 * c], A.cams[4 * c + 1], A.cams[4 * c + 2], A.cams[4 * c + 3], p);
         A.pts[3 * row] = p[0]; A.pts[3 * row + 1] = p[1]; A.pts[3 * row + 2] = p[2];
     }
+}
+
+// The sub-pixel offsets of the keypoints of a batch of response maps (the rule: feat_pyr_subpix): a thread per keypoint,
+// five loads of R.
+__global__ __launch_bounds__(256) void feat_pyr_subpix_kernel(const int32_t *__restrict__ R, const int64_t *__restrict__ off,
+                                                              const int32_t *__restrict__ hw, FeatKeypoints K, double *__restrict__ offs) {
+    const int c = blockIdx.y;
+    int64_t row;
+    if (!feat_keypoint_row(K, c, (int64_t)blockIdx.x * 256 + threadIdx.x, &row)) return;
+    const FeatImage im = feat_image(off, hw, c);
+    double o[2];
+    feat_pyr_subpix(R + im.base, im.H, im.W, K.kp[2 * row], K.kp[2 * row + 1], o);
+    offs[2 * row] = o[0]; offs[2 * row + 1] = o[1];
 }
 
 // The merge's point rule on the Z the stereo kernel left in the rows (cams: five numbers per frame): X and Y move from the
@@ -690,6 +712,12 @@ static void feat_launch_points(const float *depth, const int64_t *off, const int
                                const double *cams, double *pts, hipStream_t st) {
     if (most > 0)
         hipLaunchKernelGGL(feat_points_kernel, dim3((unsigned)ceil_div64(most, 256), (unsigned)n), dim3(256), 0, st, depth, off, hw, K, cams, pts);
+}
+
+static void feat_launch_subpix(const int32_t *R, const int64_t *off, const int32_t *hw, int n, const FeatKeypoints &K, int64_t most,
+                               double *offs, hipStream_t st) {
+    if (most > 0)
+        hipLaunchKernelGGL(feat_pyr_subpix_kernel, dim3((unsigned)ceil_div64(most, 256), (unsigned)n), dim3(256), 0, st, R, off, hw, K, offs);
 }
 
 static void feat_launch_stereo(const uint8_t *left, const uint8_t *right, const int64_t *off, const int32_t *hw, int n, const FeatKeypoints &K,
@@ -773,6 +801,22 @@ CSLAM_API int cslam_feat_points_dev(const float *d_depth, const int64_t *d_off, 
     PTR_DEVICE(d_depth);
     FeatKeypoints K = {d_kp, d_kp_off, nullptr, 0};
     feat_launch_points(d_depth, d_off, d_hw, n, K, ks.largest, d_cameras, d_points, (hipStream_t)stream);
+    HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_subpixel_dev(const int32_t *d_R, const int64_t *d_off, const int32_t *d_hw, int n, const int32_t *d_kp,
+                                      const int64_t *d_kp_off, double *d_offsets, const int64_t *h_off, const int32_t *h_hw,
+                                      const int64_t *h_kp_off, void *stream) {
+    FeatShape sh;
+    RaggedShape ks;
+    int rc = feat_shape(h_off, h_hw, n, &sh);
+    if (rc) return rc;
+    if ((rc = feat_kp_shape(h_kp_off, n, &ks))) return rc;
+    ARG_CHECK(d_R && d_off && d_hw && d_kp && d_kp_off && d_offsets, "NULL argument");
+    PTR_DEVICE(d_R);
+    FeatKeypoints K = {d_kp, d_kp_off, nullptr, 0};
+    feat_launch_subpix(d_R, d_off, d_hw, n, K, ks.largest, d_offsets, (hipStream_t)stream);
     HIP_TRY(hipGetLastError());
     return CSLAM_OK;
 }
@@ -987,7 +1031,7 @@ CSLAM_API int cslam_feat_pyramid_merge_dev(const int32_t *d_lvl_count, const int
 
 // what both pyramid chains share up to the per-level rows: level images (and maps), response, selection with the largest
 // budget (a level's first rows are its selection at any smaller one), bins and descriptors on the level images
-struct FeatPyrRows { uint8_t *gray; int32_t *count, *kp, *resp, *bins; uint8_t *desc; int stride; };
+struct FeatPyrRows { uint8_t *gray; int32_t *count, *kp, *resp, *bins; uint8_t *desc; int stride; double *loff; };   // loff: NULL = integer keypoints
 
 static int feat_pyr_rows(const uint8_t *gray0, const float *mask_depth, const int64_t *d_off, const int32_t *d_hw, int n, int levels,
                          const int64_t *d_lvl_off, const int32_t *d_lvl_hw, const FeatPyrLayout &P, double quality, int min_distance,
@@ -1001,11 +1045,12 @@ static int feat_pyr_rows(const uint8_t *gray0, const float *mask_depth, const in
                        rows.stride, s, rows.count, rows.kp, rows.resp, st);
     FeatKeypoints K = {rows.kp, nullptr, rows.count, rows.stride};
     feat_launch_describe(rows.gray, d_lvl_off, d_lvl_hw, nl, K, rows.stride, rows.bins, rows.desc, st);
+    if (rows.loff) feat_launch_subpix(R, d_lvl_off, d_lvl_hw, nl, K, rows.stride, rows.loff, st);
     return CSLAM_OK;
 }
 
-static void feat_pyr_rows_carve(Carver &cv, const FeatPyrLayout &P, int nl, bool maps, uint8_t **lvl_valid, int32_t **R, int32_t **rmax,
-                                FeatSelScratch *s, FeatPyrRows *rows) {
+static void feat_pyr_rows_carve(Carver &cv, const FeatPyrLayout &P, int nl, bool maps, bool subpixel, uint8_t **lvl_valid, int32_t **R,
+                                int32_t **rmax, FeatSelScratch *s, FeatPyrRows *rows) {
     const size_t total = (size_t)P.sh.px.total, r = (size_t)nl * rows->stride;
     rows->gray = cv.take<uint8_t>(total);
     *lvl_valid = maps ? cv.take<uint8_t>(total) : nullptr;
@@ -1017,15 +1062,16 @@ static void feat_pyr_rows_carve(Carver &cv, const FeatPyrLayout &P, int nl, bool
     rows->resp = cv.take<int32_t>(r);
     rows->bins = cv.take<int32_t>(r);
     rows->desc = cv.take<uint8_t>(FEAT_DESC_BYTES * r);
+    rows->loff = subpixel ? cv.take<double>(2 * r) : nullptr;
 }
 
-CSLAM_API int cslam_feat_extract_pyramid_dev(const uint8_t *d_src, const int64_t *d_src_off, const float *d_depth, const int64_t *d_off,
-                                             const int32_t *d_hw, const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
-                                             const int32_t *d_lvl_hw, double quality_level, int min_distance, int border, int max_features,
-                                             int depth_as_mask, int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels,
-                                             int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc, double *d_points, const int64_t *h_src_off,
-                                             const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
-                                             void *stream) {
+// both pyramid chains, with and without sub-pixel keypoints: d_offsets NULL = the integer keypoints
+static int feat_extract_pyramid(const uint8_t *d_src, const int64_t *d_src_off, const float *d_depth, const int64_t *d_off,
+                                const int32_t *d_hw, const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
+                                const int32_t *d_lvl_hw, double quality_level, int min_distance, int border, int max_features,
+                                int depth_as_mask, int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels, int32_t *d_resp,
+                                int32_t *d_bins, uint8_t *d_desc, double *d_points, double *d_offsets, const int64_t *h_src_off,
+                                const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw, void *stream) {
     FeatShape sh;
     FeatPyrLayout P;
     int rc = feat_shape(h_off, h_hw, n, &sh);
@@ -1046,7 +1092,7 @@ CSLAM_API int cslam_feat_extract_pyramid_dev(const uint8_t *d_src, const int64_t
     int32_t *R, *rmax;
     auto layout = [&](Carver &cv) {
         gray = cv.take<uint8_t>((size_t)sh.px.total);
-        feat_pyr_rows_carve(cv, P, n * levels, depth_as_mask != 0, &lvl_valid, &R, &rmax, &s, &rows);
+        feat_pyr_rows_carve(cv, P, n * levels, depth_as_mask != 0, d_offsets != nullptr, &lvl_valid, &R, &rmax, &s, &rows);
     };
     SCRATCH_CARVE(g_feat_scratch, st, (size_t)1 << 20, layout);
     feat_launch_gray(d_src, d_src_off, d_off, n, sh, gray, st);
@@ -1054,22 +1100,48 @@ CSLAM_API int cslam_feat_extract_pyramid_dev(const uint8_t *d_src, const int64_t
                             border, lvl_valid, R, rmax, s, rows, st)))
         return rc;
     FeatPyrMergeArgs a = {rows.count, rows.kp, rows.resp, rows.bins, rows.desc, rows.stride, nullptr, d_depth, d_off, d_hw, d_lvl_hw,
-                          d_cameras, levels, max_features, {0}, d_count, d_kp, d_level_kp, d_levels, nullptr, d_resp, d_bins, d_desc, d_points};
+                          d_cameras, levels, max_features, {0}, d_count, d_kp, d_level_kp, d_levels, nullptr, d_resp, d_bins, d_desc, d_points,
+                          rows.loff, d_offsets};
     feat_launch_merge(a, P, n, st);
     HIP_TRY(hipGetLastError());
     return CSLAM_OK;
 }
 
-CSLAM_API int cslam_feat_extract_stereo_pyramid_dev(const uint8_t *d_left, const int64_t *d_left_off, const uint8_t *d_right,
-                                                    const int64_t *d_right_off, const int64_t *d_off, const int32_t *d_hw,
-                                                    const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
-                                                    const int32_t *d_lvl_hw, double quality_level, int min_distance, int border,
-                                                    int max_features, int min_disparity, int max_disparity, int uniqueness, int lr_tolerance,
-                                                    int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels, int32_t *d_resp,
-                                                    int32_t *d_bins, uint8_t *d_desc, double *d_points, double *d_disparity, int32_t *d_status,
-                                                    const int64_t *h_left_off, const int64_t *h_right_off, const int64_t *h_off,
-                                                    const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
-                                                    const double *h_cameras, void *stream) {
+CSLAM_API int cslam_feat_extract_pyramid_dev(const uint8_t *d_src, const int64_t *d_src_off, const float *d_depth, const int64_t *d_off,
+                                             const int32_t *d_hw, const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
+                                             const int32_t *d_lvl_hw, double quality_level, int min_distance, int border, int max_features,
+                                             int depth_as_mask, int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels,
+                                             int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc, double *d_points, const int64_t *h_src_off,
+                                             const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
+                                             void *stream) {
+    return feat_extract_pyramid(d_src, d_src_off, d_depth, d_off, d_hw, d_cameras, n, levels, d_lvl_off, d_lvl_hw, quality_level, min_distance,
+                                border, max_features, depth_as_mask, d_count, d_kp, d_level_kp, d_levels, d_resp, d_bins, d_desc, d_points,
+                                nullptr, h_src_off, h_off, h_hw, h_lvl_off, h_lvl_hw, stream);
+}
+
+CSLAM_API int cslam_feat_extract_pyramid_subpix_dev(const uint8_t *d_src, const int64_t *d_src_off, const float *d_depth,
+                                                    const int64_t *d_off, const int32_t *d_hw, const double *d_cameras, int n, int levels,
+                                                    const int64_t *d_lvl_off, const int32_t *d_lvl_hw, double quality_level,
+                                                    int min_distance, int border, int max_features, int depth_as_mask, int32_t *d_count,
+                                                    double *d_kp, int32_t *d_level_kp, int32_t *d_levels, int32_t *d_resp, int32_t *d_bins,
+                                                    uint8_t *d_desc, double *d_points, double *d_offsets, const int64_t *h_src_off,
+                                                    const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off,
+                                                    const int32_t *h_lvl_hw, void *stream) {
+    ARG_CHECK(d_offsets != nullptr, "NULL argument");
+    return feat_extract_pyramid(d_src, d_src_off, d_depth, d_off, d_hw, d_cameras, n, levels, d_lvl_off, d_lvl_hw, quality_level, min_distance,
+                                border, max_features, depth_as_mask, d_count, d_kp, d_level_kp, d_levels, d_resp, d_bins, d_desc, d_points,
+                                d_offsets, h_src_off, h_off, h_hw, h_lvl_off, h_lvl_hw, stream);
+}
+
+static int feat_extract_stereo_pyramid(const uint8_t *d_left, const int64_t *d_left_off, const uint8_t *d_right, const int64_t *d_right_off,
+                                       const int64_t *d_off, const int32_t *d_hw, const double *d_cameras, int n, int levels,
+                                       const int64_t *d_lvl_off, const int32_t *d_lvl_hw, double quality_level, int min_distance, int border,
+                                       int max_features, int min_disparity, int max_disparity, int uniqueness, int lr_tolerance,
+                                       int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels, int32_t *d_resp,
+                                       int32_t *d_bins, uint8_t *d_desc, double *d_points, double *d_disparity, int32_t *d_status,
+                                       double *d_offsets, const int64_t *h_left_off, const int64_t *h_right_off, const int64_t *h_off,
+                                       const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw, const double *h_cameras,
+                                       void *stream) {
     FeatShape sh;
     FeatPyrLayout P;
     const StereoParams SP = {min_disparity, max_disparity, uniqueness, lr_tolerance};
@@ -1095,7 +1167,7 @@ CSLAM_API int cslam_feat_extract_stereo_pyramid_dev(const uint8_t *d_left, const
         gray_l = cv.take<uint8_t>((size_t)sh.px.total);
         gray_r = cv.take<uint8_t>((size_t)sh.px.total);
         base_px = cv.take<int32_t>((size_t)n * max_features * 2);
-        feat_pyr_rows_carve(cv, P, n * levels, false, &lvl_valid, &R, &rmax, &s, &rows);
+        feat_pyr_rows_carve(cv, P, n * levels, false, d_offsets != nullptr, &lvl_valid, &R, &rmax, &s, &rows);
     };
     SCRATCH_CARVE(g_feat_scratch, st, (size_t)1 << 20, layout);
     feat_launch_gray(d_left, d_left_off, d_off, n, sh, gray_l, st);
@@ -1104,7 +1176,8 @@ CSLAM_API int cslam_feat_extract_stereo_pyramid_dev(const uint8_t *d_left, const
                             rmax, s, rows, st)))
         return rc;
     FeatPyrMergeArgs a = {rows.count, rows.kp, rows.resp, rows.bins, rows.desc, rows.stride, nullptr, nullptr, d_off, d_hw, d_lvl_hw,
-                          d_cameras, levels, max_features, {0}, d_count, d_kp, d_level_kp, d_levels, base_px, d_resp, d_bins, d_desc, nullptr};
+                          d_cameras, levels, max_features, {0}, d_count, d_kp, d_level_kp, d_levels, base_px, d_resp, d_bins, d_desc, nullptr,
+                          rows.loff, d_offsets};
     feat_launch_merge(a, P, n, st);
     // the stereo rule at the level-0 pixels under the keypoints, then X and Y of its rows at the keypoints' own coordinates
     FeatKeypoints K = {base_px, nullptr, d_count, max_features};
@@ -1113,4 +1186,38 @@ CSLAM_API int cslam_feat_extract_stereo_pyramid_dev(const uint8_t *d_left, const
                        d_cameras, max_features, d_points);
     HIP_TRY(hipGetLastError());
     return CSLAM_OK;
+}
+
+CSLAM_API int cslam_feat_extract_stereo_pyramid_dev(const uint8_t *d_left, const int64_t *d_left_off, const uint8_t *d_right,
+                                                    const int64_t *d_right_off, const int64_t *d_off, const int32_t *d_hw,
+                                                    const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
+                                                    const int32_t *d_lvl_hw, double quality_level, int min_distance, int border,
+                                                    int max_features, int min_disparity, int max_disparity, int uniqueness, int lr_tolerance,
+                                                    int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels, int32_t *d_resp,
+                                                    int32_t *d_bins, uint8_t *d_desc, double *d_points, double *d_disparity, int32_t *d_status,
+                                                    const int64_t *h_left_off, const int64_t *h_right_off, const int64_t *h_off,
+                                                    const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
+                                                    const double *h_cameras, void *stream) {
+    return feat_extract_stereo_pyramid(d_left, d_left_off, d_right, d_right_off, d_off, d_hw, d_cameras, n, levels, d_lvl_off, d_lvl_hw,
+                                       quality_level, min_distance, border, max_features, min_disparity, max_disparity, uniqueness,
+                                       lr_tolerance, d_count, d_kp, d_level_kp, d_levels, d_resp, d_bins, d_desc, d_points, d_disparity,
+                                       d_status, nullptr, h_left_off, h_right_off, h_off, h_hw, h_lvl_off, h_lvl_hw, h_cameras, stream);
+}
+
+CSLAM_API int cslam_feat_extract_stereo_pyramid_subpix_dev(const uint8_t *d_left, const int64_t *d_left_off, const uint8_t *d_right,
+                                                           const int64_t *d_right_off, const int64_t *d_off, const int32_t *d_hw,
+                                                           const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
+                                                           const int32_t *d_lvl_hw, double quality_level, int min_distance, int border,
+                                                           int max_features, int min_disparity, int max_disparity, int uniqueness,
+                                                           int lr_tolerance, int32_t *d_count, double *d_kp, int32_t *d_level_kp,
+                                                           int32_t *d_levels, int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc,
+                                                           double *d_points, double *d_disparity, int32_t *d_status, double *d_offsets,
+                                                           const int64_t *h_left_off, const int64_t *h_right_off, const int64_t *h_off,
+                                                           const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
+                                                           const double *h_cameras, void *stream) {
+    ARG_CHECK(d_offsets != nullptr, "NULL argument");
+    return feat_extract_stereo_pyramid(d_left, d_left_off, d_right, d_right_off, d_off, d_hw, d_cameras, n, levels, d_lvl_off, d_lvl_hw,
+                                       quality_level, min_distance, border, max_features, min_disparity, max_disparity, uniqueness,
+                                       lr_tolerance, d_count, d_kp, d_level_kp, d_levels, d_resp, d_bins, d_desc, d_points, d_disparity,
+                                       d_status, d_offsets, h_left_off, h_right_off, h_off, h_hw, h_lvl_off, h_lvl_hw, h_cameras, stream);
 }

@@ -11,6 +11,11 @@
 //   base coord  the level-0 coordinate of level pixel x: (double)((2 x + 1) n_0) / (double)(2 n_l) - 0.5; x at level 0
 //   budgets     w_l = 5^l 6^(L - 1 - l); level l gets max_features w_l / sum w, the remainder goes to level 0
 //   point       X = ((kx - cx) Z) / fx, Y = ((ky - cy) Z) / fy on the base coordinates; an invalid Z gives a NaN row
+//   sub-pixel   per axis, from the int32 responses m, c, p of the level's map at the keypoint's two neighbours along the axis
+//               and at the keypoint: den = m - 2 c + p and num = m - p in int64; den >= 0 (a plateau, or no maximum along the
+//               axis) or a neighbour outside the image: off = 0; else off = (double)num / (double)(2 den), one division,
+//               clamped to [-0.5, 0.5].  Level-0 coordinate: ((double)(2 x + 1) + 2 off) (double)n_0 / (double)(2 n_l) - 0.5
+//               in this order; no product feeds an addition, so contraction changes no bit, and off = 0 gives base coord.
 #pragma once
 #include "feat.h"
 
@@ -47,6 +52,27 @@ FEAT_HD int feat_pyr_base_pixel(int x, int n_0, int n_l) { return (int)(((int64_
 
 FEAT_HD double feat_pyr_base_coord(int x, int n_0, int n_l) {
     return (double)((int64_t)(2 * x + 1) * n_0) / (double)(2 * (int64_t)n_l) - 0.5;
+}
+
+// the offset of a maximum along one axis from the responses before, at and after it
+FEAT_HD double feat_pyr_subpix_offset(int32_t m, int32_t c, int32_t p) {
+    const int64_t den = (int64_t)m - 2 * (int64_t)c + (int64_t)p, num = (int64_t)m - (int64_t)p;
+    if (den >= 0) return 0.0;
+    const double off = (double)num / (double)(2 * den);
+    return off < -0.5 ? -0.5 : (off > 0.5 ? 0.5 : off);
+}
+
+// both offsets of the keypoint (x, y) of an H x W response map R; an axis whose neighbour lies outside the image gives 0
+FEAT_HD void feat_pyr_subpix(const int32_t *R, int H, int W, int x, int y, double *off) {
+    off[0] = off[1] = 0.0;
+    if (x < 0 || x >= W || y < 0 || y >= H) return;
+    const int32_t *r = R + (int64_t)y * W + x;
+    if (x >= 1 && x + 1 < W) off[0] = feat_pyr_subpix_offset(r[-1], r[0], r[1]);
+    if (y >= 1 && y + 1 < H) off[1] = feat_pyr_subpix_offset(r[-(int64_t)W], r[0], r[W]);
+}
+
+FEAT_HD double feat_pyr_subpix_coord(int x, double off, int n_0, int n_l) {
+    return ((double)(2 * (int64_t)x + 1) + 2.0 * off) * (double)n_0 / (double)(2 * (int64_t)n_l) - 0.5;
 }
 
 FEAT_HD void feat_pyr_budgets(int max_features, int levels, int *budget) {

@@ -27,6 +27,11 @@
 //               fit: it wants six correspondences and tests det A against an ABSOLUTE 1e-6, which in pixel units (entries
 //               of A near 1e5) the rounding noise of a rank-deficient A exceeds by many orders.  Here: singular, and
 //               delta = 0, where a pivot is not above PNP_PIVOT_REL times its diagonal entry or anything is non-finite.
+//   levels      the level-aware form (keypoints of a scale pyramid): sigma2[l] = (double)36^l / (double)25^l for l = 0 .. 7,
+//               exact integers and one division.  A correspondence whose "to" keypoint has level l is an inlier iff its depth
+//               is positive and e2 <= thr2 sigma2[l], in hypothesis scoring, in the inlier set of the best hypothesis and in
+//               every recount; each of its 27 Gauss-Newton terms is multiplied by 1 / sigma2[l].  Sampler, P3P, selection
+//               by the fourth point, the best key, the stopping rule and the status rules are those above.
 #pragma once
 #include <math.h>
 #include <stdint.h>
@@ -42,6 +47,7 @@
 #define PNP_COLLINEAR 1e-20        // |d12 x d13|^2 <= this * a12 * a13: no solution attempted
 #define PNP_PIVOT_REL 1e-11        // an LDL^T pivot at or below this share of its diagonal entry: singular
 #define PNP_NSUM 27
+#define PNP_MAX_LEVEL 7
 
 PNP_HD bool pnp_finite(double v) { return fabs(v) <= 1.7976931348623157e308; }   // false for NaN
 
@@ -276,6 +282,18 @@ PNP_HD bool pnp_inlier(const double *R, const double *t, const double *cam, cons
     return pnp_reproject(R, t, cam, x, u, v, &e2) && e2 <= thr2;
 }
 
+// sigma2 of level l in [0, PNP_MAX_LEVEL]: 36^l and 25^l are integers below 2^53
+PNP_HD double pnp_level_sigma2(int l) {
+    int64_t num = 1, den = 1;
+    for (int i = 0; i < l; ++i) { num *= 36; den *= 25; }
+    return (double)num / (double)den;
+}
+PNP_HD bool pnp_inlier_level(const double *R, const double *t, const double *cam, const double *x, double u, double v, double thr2,
+                             double sigma2) {
+    double e2;
+    return pnp_reproject(R, t, cam, x, u, v, &e2) && e2 <= thr2 * sigma2;
+}
+
 // the root a fourth correspondence picks; -1 for n == 0
 PNP_HD int pnp_select(int n, const double *Rs, const double *ts, const double *cam, const double *x4, double u4, double v4) {
     int best = -1;
@@ -304,21 +322,41 @@ PNP_HD bool pnp_hypothesis(const double *X4, const double *uv4, const double *ca
     return true;
 }
 
-// adds one correspondence's 27 terms to s; a point whose depth under (R, t) is not positive adds nothing
-PNP_HD void pnp_gn_accumulate(const double *R, const double *t, const double *cam, const double *x, double u, double v, double *s) {
+// the rows Ju, Jv of J and the residual (ru, rv) of one correspondence; false where its depth under (R, t) is not positive
+PNP_HD bool pnp_gn_rows(const double *R, const double *t, const double *cam, const double *x, double u, double v, double *Ju, double *Jv,
+                        double *ru, double *rv) {
     const double px = R[0] * x[0] + R[1] * x[1] + R[2] * x[2] + t[0];
     const double py = R[3] * x[0] + R[4] * x[1] + R[5] * x[2] + t[1];
     const double pz = R[6] * x[0] + R[7] * x[1] + R[8] * x[2] + t[2];
-    if (!(pz > 0.0)) return;
+    if (!(pz > 0.0)) return false;
     const double iz = 1.0 / pz, a = cam[0] * iz, b = cam[1] * iz, xz = px * iz, yz = py * iz;
     // Jpi = [[a, 0, -a xz], [0, b, -b yz]],  dp / d delta = [-[p]x, I]
-    const double Ju[6] = {-a * xz * py, a * (pz + xz * px), -a * py, a, 0.0, -a * xz};
-    const double Jv[6] = {-b * (pz + yz * py), b * yz * px, b * px, 0.0, b, -b * yz};
-    const double ru = cam[0] * xz + cam[2] - u, rv = cam[1] * yz + cam[3] - v;
+    Ju[0] = -a * xz * py; Ju[1] = a * (pz + xz * px); Ju[2] = -a * py; Ju[3] = a; Ju[4] = 0.0; Ju[5] = -a * xz;
+    Jv[0] = -b * (pz + yz * py); Jv[1] = b * yz * px; Jv[2] = b * px; Jv[3] = 0.0; Jv[4] = b; Jv[5] = -b * yz;
+    *ru = cam[0] * xz + cam[2] - u;
+    *rv = cam[1] * yz + cam[3] - v;
+    return true;
+}
+
+// adds one correspondence's 27 terms to s; a point whose depth under (R, t) is not positive adds nothing
+PNP_HD void pnp_gn_accumulate(const double *R, const double *t, const double *cam, const double *x, double u, double v, double *s) {
+    double Ju[6], Jv[6], ru, rv;
+    if (!pnp_gn_rows(R, t, cam, x, u, v, Ju, Jv, &ru, &rv)) return;
     int k = 0;
     for (int i = 0; i < 6; ++i)
         for (int j = i; j < 6; ++j) s[k++] += Ju[i] * Ju[j] + Jv[i] * Jv[j];
     for (int i = 0; i < 6; ++i) s[21 + i] += Ju[i] * ru + Jv[i] * rv;
+}
+
+// the level-aware form: every term times w = 1 / sigma2 of the correspondence's level
+PNP_HD void pnp_gn_accumulate_level(const double *R, const double *t, const double *cam, const double *x, double u, double v, double w,
+                                    double *s) {
+    double Ju[6], Jv[6], ru, rv;
+    if (!pnp_gn_rows(R, t, cam, x, u, v, Ju, Jv, &ru, &rv)) return;
+    int k = 0;
+    for (int i = 0; i < 6; ++i)
+        for (int j = i; j < 6; ++j) s[k++] += (Ju[i] * Ju[j] + Jv[i] * Jv[j]) * w;
+    for (int i = 0; i < 6; ++i) s[21 + i] += (Ju[i] * ru + Jv[i] * rv) * w;
 }
 
 // delta = -A^-1 b of the 27 sums; false (singular) and delta = 0 by the rule above

@@ -19,6 +19,9 @@
 //                        C: the best (inlier count, then lowest h) by a packed integer max; D: rounds of Gauss-Newton on
 //                        the inlier set and a recount: lanes stride over the points, a fixed shuffle tree per wave, the
 //                        waves added in wave order by thread 0, which solves and broadcasts.
+//                        vis_pnp_kernel<true> is the level-aware form (pnp.h): sigma2 of each correspondence's "to" level
+//                        lies beside it in LDS as a float64 (16 KiB more: 106 KiB), which scales its inlier threshold and
+//                        divides its Gauss-Newton terms; vis_pnp_kernel<false> compiles to what it was without the form.
 // No float atomics; every floating sum has a fixed order: a pair's bytes are the same alone or in any batch.  A batch of P
 // pairs occupies P workgroups in the PnP kernel, so a small batch leaves most of the chip idle (accepted: DESIGN.md).
 #include "common.h"
@@ -32,6 +35,7 @@
 #define VIS_WAVES (VIS_BLOCK / 64)
 #define VIS_GN_TOL 1e-10
 #define VIS_PNP_LDS (5 * VIS_MAX_CORR * 8 + VIS_MAX_CORR * 4 + VIS_MAX_CORR)
+#define VIS_PNP_LEVELS_LDS (VIS_PNP_LDS + VIS_MAX_CORR * 8)
 
 typedef unsigned long long u64;
 
@@ -107,6 +111,7 @@ struct VisPnpArgs {
     u64 seed;
     double *T; int32_t *info; int32_t *flags;              // [n_pairs, 16], [n_pairs, 8], [total rows]
     double *hyp_pose; int32_t *hyp_info;                   // NULL, or [n_pairs, iterations, 12] and [n_pairs, iterations, 2]
+    const int32_t *lvl;                                    // the level-aware form: the level of every "to" row, in the layout of pix
 };
 
 __device__ __forceinline__ int vis_block_count(bool x, int *s_w, int t) {
@@ -119,11 +124,20 @@ __device__ __forceinline__ int vis_block_count(bool x, int *s_w, int t) {
     return n;
 }
 
-__global__ __launch_bounds__(VIS_BLOCK) void vis_pnp_kernel(VisPnpArgs A) {
+// the inlier rule of correspondence k; sW: sigma2 per correspondence (the level-aware form only)
+template <bool LEVELS>
+__device__ __forceinline__ bool vis_inlier(const double *R, const double *t, const double *cam, const double *x, double u, double v,
+                                           double thr2, const double *sW, int k) {
+    if constexpr (LEVELS) return pnp_inlier_level(R, t, cam, x, u, v, thr2, sW[k]);
+    else return pnp_inlier(R, t, cam, x, u, v, thr2);
+}
+
+template <bool LEVELS> __global__ __launch_bounds__(VIS_BLOCK) void vis_pnp_kernel(VisPnpArgs A) {
     extern __shared__ __attribute__((aligned(16))) char vis_smem[];
     double *sX = (double *)vis_smem, *sY = sX + VIS_MAX_CORR, *sZ = sY + VIS_MAX_CORR, *sU = sZ + VIS_MAX_CORR, *sV = sU + VIS_MAX_CORR;
     int32_t *s_src = (int32_t *)(sV + VIS_MAX_CORR);
     uint8_t *s_inl = (uint8_t *)(s_src + VIS_MAX_CORR);
+    double *sW = LEVELS ? (double *)(s_inl + VIS_MAX_CORR) : nullptr;      // sigma2 per correspondence; the uniform form has no room for it
     __shared__ int s_w[VIS_WAVES];
     __shared__ u64 s_key[VIS_WAVES];
     __shared__ double s_sum[VIS_WAVES][PNP_NSUM];
@@ -144,12 +158,14 @@ __global__ __launch_bounds__(VIS_BLOCK) void vis_pnp_kernel(VisPnpArgs A) {
         const int64_t k = c0 + t;
         bool ok = false;
         double x[3] = {0.0, 0.0, 0.0}, u = 0.0, v = 0.0;
+        int lv = 0;
         if (k < given) {
             A.flags[r0 + k] = 0;
             const int64_t i = A.rows[2 * (r0 + k)], j = A.rows[2 * (r0 + k) + 1];
             if (i >= 0 && i < np_ && j >= 0 && j < nx_) {  // a row that points outside its keyframes is dropped
                 for (int a = 0; a < 3; ++a) x[a] = A.pts[3 * (p0 + i) + a];
                 u = A.pix[2 * (x0 + j)]; v = A.pix[2 * (x0 + j) + 1];
+                if constexpr (LEVELS) lv = A.lvl[x0 + j];
                 ok = pnp_finite(x[0]) && pnp_finite(x[1]) && pnp_finite(x[2]) && pnp_finite(u) && pnp_finite(v);
             }
         }
@@ -160,6 +176,10 @@ __global__ __launch_bounds__(VIS_BLOCK) void vis_pnp_kernel(VisPnpArgs A) {
         int at = M + (int)__popcll(m & ((1ull << lane) - 1ull));
         for (int w = 0; w < wave; ++w) at += s_w[w];
         if (ok && at < VIS_MAX_CORR) { sX[at] = x[0]; sY[at] = x[1]; sZ[at] = x[2]; sU[at] = u; sV[at] = v; s_src[at] = (int)k; }
+        // The host refused levels outside 0 .. PNP_MAX_LEVEL on h_levels_to; the device copy is trusted to equal that checked copy,
+        // and the clamp only bounds the loop of pnp_level_sigma2 should a caller break that.
+        if constexpr (LEVELS)
+            if (ok && at < VIS_MAX_CORR) sW[at] = pnp_level_sigma2(lv < 0 ? 0 : (lv > PNP_MAX_LEVEL ? PNP_MAX_LEVEL : lv));
         for (int w = 0; w < VIS_WAVES; ++w) M += s_w[w];
     }
     __syncthreads();
@@ -201,7 +221,7 @@ __global__ __launch_bounds__(VIS_BLOCK) void vis_pnp_kernel(VisPnpArgs A) {
         if (valid)
             for (int k = 0; k < M; ++k) {
                 const double x[3] = {sX[k], sY[k], sZ[k]};
-                cnt += pnp_inlier(R, tt, cam, x, sU[k], sV[k], A.thr2) ? 1 : 0;
+                cnt += vis_inlier<LEVELS>(R, tt, cam, x, sU[k], sV[k], A.thr2, sW, k) ? 1 : 0;
             }
         const u64 key = ((u64)cnt << 32) | (u64)(0x7fffffff - h);
         if (key > best_key) {
@@ -243,7 +263,7 @@ __global__ __launch_bounds__(VIS_BLOCK) void vis_pnp_kernel(VisPnpArgs A) {
         bool in = false;
         if (k < M && have) {
             const double x[3] = {sX[k], sY[k], sZ[k]};
-            in = pnp_inlier(R, tt, cam, x, sU[k], sV[k], A.thr2);
+            in = vis_inlier<LEVELS>(R, tt, cam, x, sU[k], sV[k], A.thr2, sW, k);
         }
         if (k < M) s_inl[k] = in ? 1 : 0;
         inliers += vis_block_count(in, s_w, t);
@@ -256,7 +276,8 @@ __global__ __launch_bounds__(VIS_BLOCK) void vis_pnp_kernel(VisPnpArgs A) {
             for (int k = t; k < M; k += VIS_BLOCK)
                 if (s_inl[k]) {
                     const double x[3] = {sX[k], sY[k], sZ[k]};
-                    pnp_gn_accumulate(R, tt, cam, x, sU[k], sV[k], s);
+                    if constexpr (LEVELS) pnp_gn_accumulate_level(R, tt, cam, x, sU[k], sV[k], 1.0 / sW[k], s);
+                    else pnp_gn_accumulate(R, tt, cam, x, sU[k], sV[k], s);
                 }
 #pragma unroll
             for (int e = 0; e < PNP_NSUM; ++e) {
@@ -306,7 +327,7 @@ __global__ __launch_bounds__(VIS_BLOCK) void vis_pnp_kernel(VisPnpArgs A) {
             bool in = false;
             if (k < M) {
                 const double x[3] = {sX[k], sY[k], sZ[k]};
-                in = pnp_inlier(R, tt, cam, x, sU[k], sV[k], A.thr2);
+                in = vis_inlier<LEVELS>(R, tt, cam, x, sU[k], sV[k], A.thr2, sW, k);
                 s_inl[k] = in ? 1 : 0;
             }
             inliers += vis_block_count(in, s_w, t);
@@ -373,15 +394,28 @@ static int vis_launch_match(const uint8_t *da, const int64_t *a_off, const uint8
     return CSLAM_OK;
 }
 
-static int vis_launch_pnp(const VisPnpArgs &a, int n_pairs, hipStream_t st) {
+template <bool LEVELS> static int vis_launch_pnp_form(const VisPnpArgs &a, int n_pairs, hipStream_t st) {
+    constexpr int lds = LEVELS ? VIS_PNP_LEVELS_LDS : VIS_PNP_LDS;
     static DeviceOnce once;
     int dev;
     if (once.todo(&dev)) {
-        HIP_TRY(hipFuncSetAttribute((const void *)vis_pnp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, VIS_PNP_LDS));
+        HIP_TRY(hipFuncSetAttribute((const void *)vis_pnp_kernel<LEVELS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         once.done(dev);
     }
-    hipLaunchKernelGGL(vis_pnp_kernel, dim3((unsigned)n_pairs), dim3(VIS_BLOCK), VIS_PNP_LDS, st, a);
+    hipLaunchKernelGGL(vis_pnp_kernel<LEVELS>, dim3((unsigned)n_pairs), dim3(VIS_BLOCK), lds, st, a);
     HIP_TRY(hipGetLastError());
+    return CSLAM_OK;
+}
+
+static int vis_launch_pnp(const VisPnpArgs &a, int n_pairs, hipStream_t st) {
+    return a.lvl ? vis_launch_pnp_form<true>(a, n_pairs, st) : vis_launch_pnp_form<false>(a, n_pairs, st);
+}
+
+// the levels of the "to" rows on the host: each in 0 .. PNP_MAX_LEVEL, refused before any launch
+static int vis_levels_check(const int32_t *h_levels_to, const int64_t *h_to_off, int n_pairs) {
+    ARG_CHECK(h_levels_to != nullptr && h_to_off != nullptr, "h_levels_to and the host offsets of the \"to\" rows are required");
+    for (int64_t i = 0; i < h_to_off[n_pairs]; ++i)
+        ARG_CHECK(h_levels_to[i] >= 0 && h_levels_to[i] <= PNP_MAX_LEVEL, "levels must be in [0, 7]");
     return CSLAM_OK;
 }
 
@@ -413,12 +447,33 @@ CSLAM_API int cslam_vis_pnp_dev(const double *d_points, const int64_t *d_points_
     return vis_launch_pnp(a, n_pairs, (hipStream_t)stream);
 }
 
-CSLAM_API int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d_points_from, const int64_t *d_from_off,
-                                     const uint8_t *d_desc_to, const double *d_pixels_to, const int64_t *d_to_off,
-                                     const double *d_cameras, int n_pairs, int desc_bytes, double nndr, int iterations,
-                                     double reproj_error, int min_inliers, int refine_iterations, int refine_rounds, uint64_t seed,
-                                     int32_t *d_rows, int32_t *d_count, double *d_T, int32_t *d_info, int32_t *d_flags,
-                                     const int64_t *h_from_off, const int64_t *h_to_off, void *stream) {
+CSLAM_API int cslam_vis_pnp_levels_dev(const double *d_points, const int64_t *d_points_off, const double *d_pixels,
+                                       const int64_t *d_pixels_off, const int32_t *d_levels_to, const int32_t *d_rows,
+                                       const int64_t *d_row_off, const int32_t *d_count, const double *d_cameras, int n_pairs,
+                                       int iterations, double reproj_error, int min_inliers, int refine_iterations, int refine_rounds,
+                                       uint64_t seed, double *d_T, int32_t *d_info, int32_t *d_flags, const int64_t *h_pixels_off,
+                                       const int32_t *h_levels_to, void *stream) {
+    int rc = vis_pnp_checks(n_pairs, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds);
+    if (rc) return rc;
+    ARG_CHECK(d_points && d_points_off && d_pixels && d_pixels_off && d_levels_to && d_rows && d_row_off && d_cameras && d_T && d_info &&
+              d_flags, "NULL argument");
+    RaggedShape to;
+    if ((rc = vis_shape(h_pixels_off, n_pairs, "h_pixels_off is required", &to))) return rc;
+    if ((rc = vis_levels_check(h_levels_to, h_pixels_off, n_pairs))) return rc;
+    PTR_DEVICE(d_points);
+    VisPnpArgs a = {d_points, d_points_off, d_pixels, d_pixels_off, d_rows, d_row_off, d_count, d_cameras, iterations, min_inliers,
+                    refine_iterations, refine_rounds, reproj_error * reproj_error, (u64)seed, d_T, d_info, d_flags, nullptr, nullptr,
+                    d_levels_to};
+    return vis_launch_pnp(a, n_pairs, (hipStream_t)stream);
+}
+
+// match, then PnP on the matches, chained without a host wait; d_levels_to NULL = the uniform form
+static int vis_register(const uint8_t *d_desc_from, const double *d_points_from, const int64_t *d_from_off, const uint8_t *d_desc_to,
+                        const double *d_pixels_to, const int64_t *d_to_off, const int32_t *d_levels_to, const double *d_cameras,
+                        int n_pairs, int desc_bytes, double nndr, int iterations, double reproj_error, int min_inliers,
+                        int refine_iterations, int refine_rounds, uint64_t seed, int32_t *d_rows, int32_t *d_count, double *d_T,
+                        int32_t *d_info, int32_t *d_flags, const int64_t *h_from_off, const int64_t *h_to_off, const int32_t *h_levels_to,
+                        void *stream) {
     int rc = vis_match_checks(n_pairs, desc_bytes, nndr);
     if (rc) return rc;
     if ((rc = vis_pnp_checks(n_pairs, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds))) return rc;
@@ -427,12 +482,38 @@ CSLAM_API int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d
     RaggedShape from, to;
     if ((rc = vis_shape(h_from_off, n_pairs, "h_from_off is required", &from))) return rc;
     if ((rc = vis_shape(h_to_off, n_pairs, "h_to_off is required", &to))) return rc;
+    if (d_levels_to && (rc = vis_levels_check(h_levels_to, h_to_off, n_pairs))) return rc;
     PTR_DEVICE(d_desc_from);
     hipStream_t st = (hipStream_t)stream;
     if ((rc = vis_launch_match(d_desc_from, d_from_off, d_desc_to, d_to_off, n_pairs, from, to, nndr, d_rows, d_count, st))) return rc;
     VisPnpArgs a = {d_points_from, d_from_off, d_pixels_to, d_to_off, d_rows, d_from_off, d_count, d_cameras, iterations, min_inliers,
-                    refine_iterations, refine_rounds, reproj_error * reproj_error, (u64)seed, d_T, d_info, d_flags, nullptr, nullptr};
+                    refine_iterations, refine_rounds, reproj_error * reproj_error, (u64)seed, d_T, d_info, d_flags, nullptr, nullptr,
+                    d_levels_to};
     return vis_launch_pnp(a, n_pairs, st);
+}
+
+CSLAM_API int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d_points_from, const int64_t *d_from_off,
+                                     const uint8_t *d_desc_to, const double *d_pixels_to, const int64_t *d_to_off,
+                                     const double *d_cameras, int n_pairs, int desc_bytes, double nndr, int iterations,
+                                     double reproj_error, int min_inliers, int refine_iterations, int refine_rounds, uint64_t seed,
+                                     int32_t *d_rows, int32_t *d_count, double *d_T, int32_t *d_info, int32_t *d_flags,
+                                     const int64_t *h_from_off, const int64_t *h_to_off, void *stream) {
+    return vis_register(d_desc_from, d_points_from, d_from_off, d_desc_to, d_pixels_to, d_to_off, nullptr, d_cameras, n_pairs, desc_bytes,
+                        nndr, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed, d_rows, d_count, d_T, d_info,
+                        d_flags, h_from_off, h_to_off, nullptr, stream);
+}
+
+CSLAM_API int cslam_vis_register_levels_dev(const uint8_t *d_desc_from, const double *d_points_from, const int64_t *d_from_off,
+                                            const uint8_t *d_desc_to, const double *d_pixels_to, const int64_t *d_to_off,
+                                            const int32_t *d_levels_to, const double *d_cameras, int n_pairs, int desc_bytes, double nndr,
+                                            int iterations, double reproj_error, int min_inliers, int refine_iterations, int refine_rounds,
+                                            uint64_t seed, int32_t *d_rows, int32_t *d_count, double *d_T, int32_t *d_info,
+                                            int32_t *d_flags, const int64_t *h_from_off, const int64_t *h_to_off,
+                                            const int32_t *h_levels_to, void *stream) {
+    ARG_CHECK(d_levels_to != nullptr && h_levels_to != nullptr, "d_levels_to and h_levels_to are required");
+    return vis_register(d_desc_from, d_points_from, d_from_off, d_desc_to, d_pixels_to, d_to_off, d_levels_to, d_cameras, n_pairs,
+                        desc_bytes, nndr, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed, d_rows, d_count,
+                        d_T, d_info, d_flags, h_from_off, h_to_off, h_levels_to, stream);
 }
 
 CSLAM_API int cslam_vis_hypotheses_dev(const double *d_points, const double *d_pixels, const int64_t *d_off, const double *d_cameras,

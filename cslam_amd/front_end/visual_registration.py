@@ -11,6 +11,12 @@ unpinned: the algorithm is the one include/cslam_hip.h states and tests/vis_refe
 Convention: `transformation` maps points of the "from" camera frame into the "to" camera frame.  The 3D points come from
 "from"; the pixels and the camera (fx, fy, cx, cy: pinhole, rectified, no distortion) from "to".
 
+The level-aware forms (`register_level_pairs`, `pnp_ransac_level_pairs`) are for keyframes of the scale pyramid
+(visual_pyramid.py), whose keypoints of level l are located on an image 1.2^l times coarser: with sigma2[l] = 36^l / 25^l a
+correspondence whose "to" keypoint has level l is an inlier iff its depth is positive and its squared pixel error is
+<= reproj_error^2 sigma2[l], and its Gauss-Newton terms are multiplied by 1 / sigma2[l]; everything else is the rule above
+(tests/vis_levels_reference.py restates it).  Parity with rtabmap's use of cv::KeyPoint::octave is unpinned too.
+
 There is no CPU path: without the library or a GPU the functions raise CslamHipError.
 """
 from collections import namedtuple
@@ -25,10 +31,15 @@ VIS_MATCH_BLOCK = 256          # "from" rows per workgroup of the matcher
 VIS_MATCH_CHUNK = 256          # "to" rows per LDS chunk of the matcher; the tests size around both
 VIS_MAX_CORR = 2048            # most usable correspondences of a pair the PnP kernel attempts; above it: status 3
 VIS_DESC_BYTES = 32
+VIS_MAX_LEVEL = 7              # levels of the level-aware PnP are 0 .. 7, the levels a scale pyramid can have
 
 Keyframe = namedtuple("Keyframe", "keypoints points descriptors")
 Keyframe.__doc__ = """What a keyframe carries on the wire: keypoints [n, 2] pixels, points [n, 3] in the camera frame (a row
 that is not finite: no depth), descriptors [n, 32] uint8.  float32 arrays are widened to float64 on upload."""
+
+LevelKeyframe = namedtuple("LevelKeyframe", "keypoints points descriptors levels")
+LevelKeyframe.__doc__ = """A `Keyframe` of the scale pyramid: also levels [n] uint8, the pyramid level of every keypoint (on the wire
+one byte per keypoint, the counterpart of cv::KeyPoint::octave).  `register_pairs` takes it as it is and ignores the levels."""
 
 
 class VisualRegistration:
@@ -81,6 +92,24 @@ def _keyframe(kf):
     if not (len(kp) == len(pts) == len(desc)):
         raise ValueError("a keyframe has one point and one descriptor per keypoint: %d, %d, %d" % (len(kp), len(pts), len(desc)))
     return kp, pts, desc
+
+
+def _levels(levels, n):
+    lv = np.asarray(levels)
+    if lv.ndim != 1 or len(lv) != n:
+        raise ValueError("levels are an [n] array, one per keypoint: got shape %s for %d keypoints" % (lv.shape, n))
+    if lv.dtype.kind not in "iu":
+        raise ValueError("levels are whole numbers, got %s" % lv.dtype)
+    if len(lv) and not (0 <= int(lv.min()) and int(lv.max()) <= VIS_MAX_LEVEL):
+        raise ValueError("levels must be in [0, %d]" % VIS_MAX_LEVEL)
+    return np.ascontiguousarray(lv, dtype=np.int32)
+
+
+def _level_keyframe(kf):
+    if not hasattr(kf, "levels"):
+        raise ValueError("the level-aware registration takes LevelKeyframes (keypoints, points, descriptors, levels)")
+    kp, pts, desc = _keyframe(kf)
+    return kp, pts, desc, _levels(kf.levels, len(kp))
 
 
 def _cameras(cameras, n):
@@ -174,14 +203,15 @@ def _point_pairs(pairs):
     return pts, pix
 
 
-def pnp_ransac_pairs(pairs, cameras, iterations=300, reproj_error=2.0, min_inliers=20, refine_iterations=10, refine_rounds=2, seed=0,
-                     device=0):
-    """PnP RANSAC of a list of (points3d [M, 3] in the "from" camera frame, pixels [M, 2] in the "to" image), row for row, in
-    ONE call (`cslam_vis_pnp_dev`).  `cameras`: (fx, fy, cx, cy) of the "to" cameras, one for all or one per pair.  Returns a
-    `VisualRegistration` per pair whose `matches` are (k, k)."""
+def _pnp_pairs(pairs, levels_to, cameras, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed, device):
+    """`pnp_ransac_pairs` (levels_to None) and `pnp_ransac_level_pairs`."""
     it, e, mi, ri, rr, sd = _ransac(iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed)
     pts, pix = _point_pairs(pairs)
     cam = _cameras(cameras, len(pairs))
+    if levels_to is not None:
+        if len(levels_to) != len(pairs):
+            raise ValueError("one array of levels per pair")
+        lvl = [_levels(l, len(x)) for l, x in zip(levels_to, pix)]
     with gpu(device) as (lib, dev):
         if not pairs:
             return []
@@ -190,11 +220,33 @@ def pnp_ransac_pairs(pairs, cameras, iterations=300, reproj_error=2.0, min_inlie
         rows = np.repeat(np.concatenate([np.arange(len(a), dtype=np.int32) for a in pts])[:, None], 2, axis=1)
         t_pts, t_pix, t_off, t_rows, t_cam = (to_dev(x, dev) for x in (_cat(pts, 3, np.float64), _cat(pix, 2, np.float64), off, rows, cam))
         t_T, t_info, t_flags = _outputs(n, int(off[-1]), dev)
-        _lib.check(lib.cslam_vis_pnp_dev(t_pts.data_ptr(), t_off.data_ptr(), t_pix.data_ptr(), t_off.data_ptr(), t_rows.data_ptr(),
-                                         t_off.data_ptr(), None, t_cam.data_ptr(), n, it, e, mi, ri, rr, sd, t_T.data_ptr(),
-                                         t_info.data_ptr(), t_flags.data_ptr(), stream()))
+        if levels_to is None:
+            _lib.check(lib.cslam_vis_pnp_dev(t_pts.data_ptr(), t_off.data_ptr(), t_pix.data_ptr(), t_off.data_ptr(), t_rows.data_ptr(),
+                                             t_off.data_ptr(), None, t_cam.data_ptr(), n, it, e, mi, ri, rr, sd, t_T.data_ptr(),
+                                             t_info.data_ptr(), t_flags.data_ptr(), stream()))
+        else:
+            h_lvl = np.concatenate(lvl) if int(off[-1]) else np.zeros(1, dtype=np.int32)
+            t_lvl = to_dev(h_lvl, dev)
+            _lib.check(lib.cslam_vis_pnp_levels_dev(t_pts.data_ptr(), t_off.data_ptr(), t_pix.data_ptr(), t_off.data_ptr(), t_lvl.data_ptr(),
+                                                    t_rows.data_ptr(), t_off.data_ptr(), None, t_cam.data_ptr(), n, it, e, mi, ri, rr, sd,
+                                                    t_T.data_ptr(), t_info.data_ptr(), t_flags.data_ptr(), host(off), host(h_lvl), stream()))
         T, info, flags = t_T.cpu().numpy(), t_info.cpu().numpy(), t_flags.cpu().numpy()
     return _registrations(T, info, flags, rows, off)
+
+
+def pnp_ransac_pairs(pairs, cameras, iterations=300, reproj_error=2.0, min_inliers=20, refine_iterations=10, refine_rounds=2, seed=0,
+                     device=0):
+    """PnP RANSAC of a list of (points3d [M, 3] in the "from" camera frame, pixels [M, 2] in the "to" image), row for row, in
+    ONE call (`cslam_vis_pnp_dev`).  `cameras`: (fx, fy, cx, cy) of the "to" cameras, one for all or one per pair.  Returns a
+    `VisualRegistration` per pair whose `matches` are (k, k)."""
+    return _pnp_pairs(pairs, None, cameras, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed, device)
+
+
+def pnp_ransac_level_pairs(pairs, levels_to, cameras, iterations=300, reproj_error=2.0, min_inliers=20, refine_iterations=10,
+                           refine_rounds=2, seed=0, device=0):
+    """The level-aware `pnp_ransac_pairs` in ONE call (`cslam_vis_pnp_levels_dev`): `levels_to` holds per pair the levels [M]
+    (whole numbers in 0 .. 7) of the "to" keypoints behind its pixels."""
+    return _pnp_pairs(pairs, levels_to, cameras, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed, device)
 
 
 Hypotheses = namedtuple("Hypotheses", "R t valid inliers best_hypothesis best_inliers")
@@ -222,14 +274,13 @@ def hypotheses(pair, camera, iterations=300, reproj_error=2.0, seed=0, device=0)
                       int(info[0, 5]), flags[:int(off[-1])].astype(bool))
 
 
-def register_pairs(pairs_of_keyframes, cameras, nndr=0.8, iterations=300, reproj_error=2.0, min_inliers=20, refine_iterations=10,
-                   refine_rounds=2, seed=0, device=0):
-    """Matching and PnP RANSAC of a list of (keyframe_from, keyframe_to) in ONE call (`cslam_vis_register_dev`), chained on
-    the device with no host wait between them: the matches select 3D points of "from" and pixels of "to".  Returns a
-    `VisualRegistration` per pair."""
+def _register(pairs_of_keyframes, with_levels, cameras, nndr, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed,
+              device):
+    """`register_pairs` and, `with_levels`, `register_level_pairs`."""
     r = _nndr(nndr)
     it, e, mi, ri, rr, sd = _ransac(iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed)
-    kfs = [(_keyframe(a), _keyframe(b)) for a, b in pairs_of_keyframes]
+    check = _level_keyframe if with_levels else _keyframe
+    kfs = [(check(a), check(b)) for a, b in pairs_of_keyframes]
     cam = _cameras(cameras, len(kfs))
     with gpu(device) as (lib, dev):
         import torch
@@ -245,14 +296,44 @@ def register_pairs(pairs_of_keyframes, cameras, nndr=0.8, iterations=300, reproj
         t_rows = torch.zeros((max(int(a_off[-1]), 1), 2), dtype=torch.int32, device=dev)
         t_cnt = torch.zeros(n, dtype=torch.int32, device=dev)
         t_T, t_info, t_flags = _outputs(n, int(a_off[-1]), dev)
-        _lib.check(lib.cslam_vis_register_dev(t_da.data_ptr(), t_pts.data_ptr(), t_ao.data_ptr(), t_db.data_ptr(), t_pix.data_ptr(),
-                                              t_bo.data_ptr(), t_cam.data_ptr(), n, VIS_DESC_BYTES, r, it, e, mi, ri, rr, sd,
-                                              t_rows.data_ptr(), t_cnt.data_ptr(), t_T.data_ptr(), t_info.data_ptr(), t_flags.data_ptr(),
-                                              host(a_off), host(b_off), stream()))
+        if not with_levels:
+            _lib.check(lib.cslam_vis_register_dev(t_da.data_ptr(), t_pts.data_ptr(), t_ao.data_ptr(), t_db.data_ptr(), t_pix.data_ptr(),
+                                                  t_bo.data_ptr(), t_cam.data_ptr(), n, VIS_DESC_BYTES, r, it, e, mi, ri, rr, sd,
+                                                  t_rows.data_ptr(), t_cnt.data_ptr(), t_T.data_ptr(), t_info.data_ptr(), t_flags.data_ptr(),
+                                                  host(a_off), host(b_off), stream()))
+        else:
+            h_lvl = np.concatenate([b[3] for _, b in kfs]) if int(b_off[-1]) else np.zeros(1, dtype=np.int32)
+            t_lvl = to_dev(h_lvl, dev)
+            _lib.check(lib.cslam_vis_register_levels_dev(t_da.data_ptr(), t_pts.data_ptr(), t_ao.data_ptr(), t_db.data_ptr(), t_pix.data_ptr(),
+                                                         t_bo.data_ptr(), t_lvl.data_ptr(), t_cam.data_ptr(), n, VIS_DESC_BYTES, r, it, e, mi, ri,
+                                                         rr, sd, t_rows.data_ptr(), t_cnt.data_ptr(), t_T.data_ptr(), t_info.data_ptr(),
+                                                         t_flags.data_ptr(), host(a_off), host(b_off), host(h_lvl), stream()))
         T, info, flags, rows = t_T.cpu().numpy(), t_info.cpu().numpy(), t_flags.cpu().numpy(), t_rows.cpu().numpy()
     return _registrations(T, info, flags, rows, a_off)
+
+
+def register_pairs(pairs_of_keyframes, cameras, nndr=0.8, iterations=300, reproj_error=2.0, min_inliers=20, refine_iterations=10,
+                   refine_rounds=2, seed=0, device=0):
+    """Matching and PnP RANSAC of a list of (keyframe_from, keyframe_to) in ONE call (`cslam_vis_register_dev`), chained on
+    the device with no host wait between them: the matches select 3D points of "from" and pixels of "to".  Returns a
+    `VisualRegistration` per pair."""
+    return _register(pairs_of_keyframes, False, cameras, nndr, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed,
+                     device)
+
+
+def register_level_pairs(pairs_of_level_keyframes, cameras, nndr=0.8, iterations=300, reproj_error=2.0, min_inliers=20,
+                         refine_iterations=10, refine_rounds=2, seed=0, device=0):
+    """`register_pairs` on `LevelKeyframe`s with the level-aware PnP in ONE call (`cslam_vis_register_levels_dev`): the match
+    is unchanged; the levels of the "to" keyframe scale the threshold and weight the refinement.  A plain `Keyframe` raises."""
+    return _register(pairs_of_level_keyframes, True, cameras, nndr, iterations, reproj_error, min_inliers, refine_iterations, refine_rounds,
+                     seed, device)
 
 
 def compute_transformation(kf_from, kf_to, camera, **kwargs):
     """The one-pair form of `register_pairs`: what `registration_.computeTransformation(from, to, ...)` answers."""
     return register_pairs([(kf_from, kf_to)], camera, **kwargs)[0]
+
+
+def compute_level_transformation(kf_from, kf_to, camera, **kwargs):
+    """The one-pair form of `register_level_pairs`."""
+    return register_level_pairs([(kf_from, kf_to)], camera, **kwargs)[0]

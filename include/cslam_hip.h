@@ -714,6 +714,32 @@ int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d_points_fr
                            int n_pairs, int desc_bytes, double nndr, int iterations, double reproj_error, int min_inliers,
                            int refine_iterations, int refine_rounds, uint64_t seed, int32_t *d_rows, int32_t *d_count, double *d_T,
                            int32_t *d_info, int32_t *d_flags, const int64_t *h_from_off, const int64_t *h_to_off, void *stream);
+/* Level-aware PnP, for keyframes of the scale pyramid below (csrc/pnp.h; tests/vis_levels_reference.py restates it).  A
+ *   keypoint of level l is located on an image 1.2^l times coarser, so its pixel error is worth that much less:
+ *   sigma2[l] = (double)36^l / (double)25^l for l = 0 .. 7, exact integers and one division.  A correspondence whose "to"
+ *   keypoint has level l is an inlier iff its depth is positive and its squared pixel error <= reproj_error^2 sigma2[l]: in
+ *   hypothesis scoring, in the inlier set of the best hypothesis and in every recount; each of its 27 Gauss-Newton terms is
+ *   multiplied by 1 / sigma2[l].  The sampler, P3P, the selection by the fourth point, the best-hypothesis key, the stopping
+ *   rule, the status rules and the limit of 2048 are those of cslam_vis_pnp_dev; with every level 0 the rule is its rule.
+ *   Parity with rtabmap's and OpenCV's use of cv::KeyPoint::octave is unpinned like the rest. */
+/* cslam_vis_pnp_levels_dev -- the PnP RANSAC half of computeTransformation (rgbd_handler.cpp:443-445, :519-520) in the
+ *   level-aware form: cslam_vis_pnp_dev plus d_levels_to int32, the level of every "to" row in the layout of d_pixels
+ *   (d_pixels_off).  h_pixels_off and h_levels_to: the same on the host, required: a level outside 0 .. 7 is refused before
+ *   any launch. */
+int cslam_vis_pnp_levels_dev(const double *d_points, const int64_t *d_points_off, const double *d_pixels, const int64_t *d_pixels_off,
+                             const int32_t *d_levels_to, const int32_t *d_rows, const int64_t *d_row_off, const int32_t *d_count,
+                             const double *d_cameras, int n_pairs, int iterations, double reproj_error, int min_inliers,
+                             int refine_iterations, int refine_rounds, uint64_t seed, double *d_T, int32_t *d_info, int32_t *d_flags,
+                             const int64_t *h_pixels_off, const int32_t *h_levels_to, void *stream);
+/* cslam_vis_register_levels_dev -- the whole call of rgbd_handler.cpp:443-445 / :519-520 in the level-aware form: the match
+ *   of cslam_vis_register_dev, unchanged, then the level-aware PnP on its rows, chained on the stream with no host wait.
+ *   d_levels_to / h_levels_to int32 [total to]: the levels of the "to" keypoints. */
+int cslam_vis_register_levels_dev(const uint8_t *d_desc_from, const double *d_points_from, const int64_t *d_from_off,
+                                  const uint8_t *d_desc_to, const double *d_pixels_to, const int64_t *d_to_off, const int32_t *d_levels_to,
+                                  const double *d_cameras, int n_pairs, int desc_bytes, double nndr, int iterations, double reproj_error,
+                                  int min_inliers, int refine_iterations, int refine_rounds, uint64_t seed, int32_t *d_rows,
+                                  int32_t *d_count, double *d_T, int32_t *d_info, int32_t *d_flags, const int64_t *h_from_off,
+                                  const int64_t *h_to_off, const int32_t *h_levels_to, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Visual keyframes: corners, steered BRIEF-32 descriptors and 3D points from the image (csrc/feat.hip, csrc/feat.h).
@@ -753,8 +779,8 @@ int cslam_vis_register_dev(const uint8_t *d_desc_from, const double *d_points_fr
  *   k / 8 quarter turns (x, y) -> (-y, x).  Bit i = blur(p_i) < blur(q_i), bit i mod 8 of byte i / 8.
  * Points (generateKeypoints3D): depth float32 metres of the image's size, valid iff finite and > 0; in float64
  *   X = ((u - cx) d) / fx, Y = ((v - cy) d) / fy, Z = d; a keypoint without valid depth gives a NaN row.
- * Out of scope: depth images smaller than the colour image, sub-pixel refinement.  Scale pyramids: the section after the
- *   stereo keyframes. */
+ * Out of scope: depth images smaller than the colour image.  Scale pyramids and sub-pixel keypoints: the section after
+ *   the stereo keyframes. */
 /* cslam_feat_gray_dev -- the grey conversion of rgbd_handler.cpp:266-312.  d_src uint8, image c = the bytes
  *   [d_src_off[c], d_src_off[c + 1]): H W of them (one channel) or 3 H W (B, G, R interleaved).  d_gray uint8 [total pixels]. */
 int cslam_feat_gray_dev(const uint8_t *d_src, const int64_t *d_src_off, const int64_t *d_off, const int32_t *d_hw, int n,
@@ -882,7 +908,19 @@ int cslam_feat_extract_stereo_dev(const uint8_t *d_left, const int64_t *d_left_o
  *   after another); d_lvl_hw int32 [n L, 2]; d_lvl_off int64 [n L + 1] PIXEL
  *   offsets in which every image takes its H_l W_l pixels rounded up to a multiple of 4 (a thread of the level kernel
  *   stores 4 pixels as one word).  h_lvl_off / h_lvl_hw: the same on the host, required, and checked against h_hw.
- * Out of scope: a scale-aware match rule, per-level reprojection thresholds in PnP, sub-pixel refinement, dense stereo. */
+ * Sub-pixel keypoints (the *_subpix_dev chains and cslam_feat_subpixel_dev; tests/feat_subpixel_reference.py restates
+ *   them): per axis, from the int32 responses of the level's map R at the keypoint and its two neighbours along the axis,
+ *   m (before), c (at), p (after): den = m - 2 c + p and num = m - p in int64.  den >= 0 (a plateau, or no maximum along
+ *   the axis) or a neighbour outside the image: off = 0.  Otherwise off = (double)num / (double)(2 den), one division,
+ *   clamped to [-0.5, 0.5].  Level-0 coordinate, float64 in exactly this order:
+ *   kx = ((double)(2 x + 1) + 2 off) (double)W / (double)(2 W_l) - 0.5, ky likewise; with off = 0 the kx above bit for bit.
+ *   No product feeds an addition, so contraction changes no bit.  The integer level-0 pixel (px, py) under the keypoint is
+ *   unchanged: depth is read and the stereo rule evaluated there, and the point is the point rule above on the refined
+ *   (kx, ky) at that Z.  levels = 1 is the single-scale chain with sub-pixel keypoints.  Parity with OpenCV's cornerSubPix
+ *   is unpinned.
+ * Out of scope: a scale gate in the match rule (measured on the two-distance scene of the tests: at a factor wide enough
+ *   for level quantisation and depth noise, 1.3, it changes nothing), guided re-matching after the fit, dense stereo.
+ *   Per-level thresholds in PnP: cslam_vis_pnp_levels_dev above. */
 /* cslam_feat_pyramid_dev -- the level images of the pyramid under compute_local_descriptors (rgbd_handler.cpp:266-312):
  *   d_gray uint8 in the ragged layout of the feature section -> d_lvl_gray uint8 [d_lvl_off[n L]] in the level layout.
  *   d_depth NULL, or float32 [total pixels] together with d_lvl_valid uint8 in the level layout: the validity maps, written
@@ -929,6 +967,39 @@ int cslam_feat_extract_stereo_pyramid_dev(const uint8_t *d_left, const int64_t *
                                           double *d_disparity, int32_t *d_status, const int64_t *h_left_off, const int64_t *h_right_off,
                                           const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off, const int32_t *h_lvl_hw,
                                           const double *h_cameras, void *stream);
+
+/* cslam_feat_subpixel_dev -- the sub-pixel step behind generateKeypoints (rgbd_handler.cpp:266-312; rtabmap refines corners
+ *   with cornerSubPix), staged: response maps d_R int32 [total pixels] as a ragged batch (d_off, d_hw as in the feature
+ *   section: level images are images of their own), integer keypoints d_kp int32 [total, 2] with d_kp_off int64 [n + 1]
+ *   (h_kp_off: the same on the host) -> d_offsets float64 [total, 2] = (off x, off y).  A keypoint outside its image gives
+ *   (0, 0).  A thread per keypoint, five loads, no atomics. */
+int cslam_feat_subpixel_dev(const int32_t *d_R, const int64_t *d_off, const int32_t *d_hw, int n, const int32_t *d_kp,
+                            const int64_t *d_kp_off, double *d_offsets, const int64_t *h_off, const int32_t *h_hw,
+                            const int64_t *h_kp_off, void *stream);
+/* cslam_feat_extract_pyramid_subpix_dev -- compute_local_descriptors (rgbd_handler.cpp:266-312) over the pyramid with
+ *   sub-pixel keypoints: cslam_feat_extract_pyramid_dev, whose host function it shares, plus d_offsets float64
+ *   [n, max_features, 2], the offsets of every row in level pixels.  d_kp and d_points hold the refined coordinates; every
+ *   other output equals the chain without it byte for byte. */
+int cslam_feat_extract_pyramid_subpix_dev(const uint8_t *d_src, const int64_t *d_src_off, const float *d_depth, const int64_t *d_off,
+                                          const int32_t *d_hw, const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
+                                          const int32_t *d_lvl_hw, double quality_level, int min_distance, int border, int max_features,
+                                          int depth_as_mask, int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels,
+                                          int32_t *d_resp, int32_t *d_bins, uint8_t *d_desc, double *d_points, double *d_offsets,
+                                          const int64_t *h_src_off, const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off,
+                                          const int32_t *h_lvl_hw, void *stream);
+/* cslam_feat_extract_stereo_pyramid_subpix_dev -- compute_local_descriptors for a stereo frame (rgbd_handler.cpp:266-312,
+ *   stereo_handler.cpp:148-227) over the pyramid with sub-pixel keypoints: cslam_feat_extract_stereo_pyramid_dev plus
+ *   d_offsets as above.  The stereo rule still runs at the integer level-0 pixel under each keypoint. */
+int cslam_feat_extract_stereo_pyramid_subpix_dev(const uint8_t *d_left, const int64_t *d_left_off, const uint8_t *d_right,
+                                                 const int64_t *d_right_off, const int64_t *d_off, const int32_t *d_hw,
+                                                 const double *d_cameras, int n, int levels, const int64_t *d_lvl_off,
+                                                 const int32_t *d_lvl_hw, double quality_level, int min_distance, int border,
+                                                 int max_features, int min_disparity, int max_disparity, int uniqueness, int lr_tolerance,
+                                                 int32_t *d_count, double *d_kp, int32_t *d_level_kp, int32_t *d_levels, int32_t *d_resp,
+                                                 int32_t *d_bins, uint8_t *d_desc, double *d_points, double *d_disparity, int32_t *d_status,
+                                                 double *d_offsets, const int64_t *h_left_off, const int64_t *h_right_off,
+                                                 const int64_t *h_off, const int32_t *h_hw, const int64_t *h_lvl_off,
+                                                 const int32_t *h_lvl_hw, const double *h_cameras, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Dense stereo: the rule above at every pixel of a rectified pair, and the keyframe cloud made from it

@@ -3,7 +3,8 @@ apart (grey, response, selection, bins and descriptors, points) and the whole ch
 frames with a right image 12 columns apart: the stereo kernel alone on the selected keypoints and the chained stereo
 frame.  Then, in the same run, the scale pyramid (front_end/visual_pyramid.py) at 1, 4 and 8 levels on the same frames: the
 chain, the stereo chain, and its stages apart (level images with the validity maps; response, selection with the largest
-level budget, bins and descriptors on the n L level images through the single-scale entries).  Prints one JSON line.
+level budget, bins and descriptors on the n L level images through the single-scale entries), and beside each chain its
+sub-pixel form and the staged sub-pixel offsets of the selected level keypoints.  Prints one JSON line.
 
     python tools/perf_visual_features.py [--reps 30]
 """
@@ -159,17 +160,35 @@ def main():
                                                                      *rows, t_disp.data_ptr(), t_status.data_ptr(), host(src_off),
                                                                      host(src_off), *h, *hl, host(scam), stream()))
 
+            p_offs = z((batch, mf, 2), torch.float64)
+
+            def pyr_subpix_chain():
+                _lib.check(lib.cslam_feat_extract_pyramid_subpix_dev(t_src.data_ptr(), t_so.data_ptr(), t_depth.data_ptr(), t_off.data_ptr(),
+                                                                     t_hw.data_ptr(), t_cam.data_ptr(), batch, L, lv.t_off.data_ptr(),
+                                                                     lv.t_hw.data_ptr(), 0.001, 7, 19, mf, 1, *rows, p_offs.data_ptr(),
+                                                                     host(src_off), *h, *hl, stream()))
+
+            def pyr_subpix_stereo_chain():
+                _lib.check(lib.cslam_feat_extract_stereo_pyramid_subpix_dev(t_src.data_ptr(), t_so.data_ptr(), t_right.data_ptr(),
+                                                                            t_so.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(),
+                                                                            t_scam.data_ptr(), batch, L, lv.t_off.data_ptr(),
+                                                                            lv.t_hw.data_ptr(), 0.001, 7, 19, mf, 1, 128, 15, 1, *rows,
+                                                                            t_disp.data_ptr(), t_status.data_ptr(), p_offs.data_ptr(),
+                                                                            host(src_off), host(src_off), *h, *hl, host(scam), stream()))
+
             def pyr_levels():
                 _lib.check(lib.cslam_feat_pyramid_dev(t_gray.data_ptr(), t_off.data_ptr(), t_hw.data_ptr(), batch, L, t_depth.data_ptr(),
                                                       lv.t_off.data_ptr(), lv.t_hw.data_ptr(), t_lg.data_ptr(), t_lv.data_ptr(), *h, *hl,
                                                       stream()))
 
-            r = {"chain_ms": timed(pyr_chain)}
+            r = {"chain_ms": timed(pyr_chain), "subpix_chain_ms": timed(pyr_subpix_chain)}
+            r["offsets_not_zero"] = round(float((p_offs != 0).any(dim=2).sum().item()) / batch, 1)
             cnt = p_cnt.cpu().numpy()
             lev = p_lev.cpu().numpy()
             r["keypoints_per_image"] = round(float(cnt.mean()), 1)
             r["keypoints_per_level"] = np.round(np.mean([np.bincount(lev[c, :cnt[c]], minlength=L) for c in range(batch)], axis=0), 1).tolist()
             r["stereo_chain_ms"] = timed(pyr_stereo_chain)
+            r["subpix_stereo_chain_ms"] = timed(pyr_subpix_stereo_chain)
             gray()
             r["levels_ms"] = timed(pyr_levels)
             # the level images and maps packed without padding, for the single-scale entries
@@ -200,6 +219,13 @@ def main():
             top = torch.from_numpy(lv.hw[:, ::-1].copy()).to(dev).view(nl, 1, 2) - 19
             q_kp.copy_(torch.minimum(torch.clamp(q_kp, min=18), top))
             r["describe_ms"] = timed(pyr_describe)
+            q_offs = z((nl, b0, 2), torch.float64)
+
+            def pyr_subpixel():
+                _lib.check(lib.cslam_feat_subpixel_dev(q_R.data_ptr(), q_off.data_ptr(), q_hw.data_ptr(), nl, q_kp.data_ptr(), q_ko.data_ptr(),
+                                                       q_offs.data_ptr(), *hq, host(q_koff), stream()))
+
+            r["subpixel_ms"] = timed(pyr_subpixel)
             return r
 
         res = {"gray_ms": timed(gray), "response_ms": timed(response), "select_ms": timed(select)}

@@ -1,7 +1,8 @@
 """Times of the visual verification (csrc/vis.hip) by HIP events: one pair at 1000 keypoints per keyframe, batches of 16 and
-64 such pairs, the matcher and the PnP RANSAC apart and chained.  Prints one JSON line.
+64 such pairs, the matcher and the PnP RANSAC apart and chained; beside them, in the same run, the level-aware PnP and its
+chain with a level of 0 .. 3 drawn per "to" keypoint.  Prints one JSON line.
 
-    python tools/perf_visual_registration.py [--reps 20]
+    python tools/perf_visual_registration.py [--reps 30]
 """
 import argparse
 import json
@@ -16,7 +17,7 @@ sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), ".."
 
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--reps", type=int, default=20)
+    ap.add_argument("--reps", type=int, default=30)
     ap.add_argument("--keypoints", type=int, default=1000)
     args = ap.parse_args()
     import torch
@@ -43,6 +44,8 @@ def main():
         t_T = torch.zeros((batch, 16), dtype=torch.float64, device=dev)
         t_info = torch.zeros((batch, 8), dtype=torch.int32, device=dev)
         t_flags = torch.zeros(int(a_off[-1]), dtype=torch.int32, device=dev)
+        lvl = np.random.default_rng(batch).integers(0, 4, int(b_off[-1])).astype(np.int32)
+        t_lvl = to_dev(lvl, dev)
 
         def match():
             _lib.check(lib.cslam_vis_match_dev(t_da.data_ptr(), t_ao.data_ptr(), t_db.data_ptr(), t_bo.data_ptr(), batch, 32, 0.8,
@@ -58,6 +61,18 @@ def main():
                                                   t_bo.data_ptr(), t_cam.data_ptr(), batch, 32, 0.8, 300, 2.0, 20, 10, 2, 0,
                                                   t_rows.data_ptr(), t_cnt.data_ptr(), t_T.data_ptr(), t_info.data_ptr(),
                                                   t_flags.data_ptr(), host(a_off), host(b_off), stream()))
+
+        def pnp_levels():
+            _lib.check(lib.cslam_vis_pnp_levels_dev(t_pts.data_ptr(), t_ao.data_ptr(), t_pix.data_ptr(), t_bo.data_ptr(), t_lvl.data_ptr(),
+                                                    t_rows.data_ptr(), t_ao.data_ptr(), t_cnt.data_ptr(), t_cam.data_ptr(), batch, 300, 2.0, 20,
+                                                    10, 2, 0, t_T.data_ptr(), t_info.data_ptr(), t_flags.data_ptr(), host(b_off), host(lvl),
+                                                    stream()))
+
+        def chain_levels():
+            _lib.check(lib.cslam_vis_register_levels_dev(t_da.data_ptr(), t_pts.data_ptr(), t_ao.data_ptr(), t_db.data_ptr(), t_pix.data_ptr(),
+                                                         t_bo.data_ptr(), t_lvl.data_ptr(), t_cam.data_ptr(), batch, 32, 0.8, 300, 2.0, 20, 10, 2,
+                                                         0, t_rows.data_ptr(), t_cnt.data_ptr(), t_T.data_ptr(), t_info.data_ptr(),
+                                                         t_flags.data_ptr(), host(a_off), host(b_off), host(lvl), stream()))
 
         def timed(fn):
             for _ in range(3):
@@ -76,6 +91,8 @@ def main():
         res = {"match_ms": timed(match), "pnp_ms": timed(pnp), "chain_ms": timed(chain)}
         info = t_info.cpu().numpy()
         res["accepted"] = int((info[:, 0] == 0).sum())
+        res.update({"pnp_levels_ms": timed(pnp_levels), "chain_levels_ms": timed(chain_levels)})
+        res["accepted_levels"] = int((t_info.cpu().numpy()[:, 0] == 0).sum())
         res["matches_per_pair"] = round(float(t_cnt.cpu().numpy().mean()), 1)
         out["batch_%d" % batch] = res
     print(json.dumps(out))

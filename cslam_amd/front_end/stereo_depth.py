@@ -13,7 +13,9 @@ in numpy and agrees bit for bit.  Unpinned: parity with rtabmap's or OpenCV's de
 Images are uint8 [H, W] or [H, W, 3] (B, G, R), the two sides of a frame of the same H x W (they may differ in channels);
 a camera is (fx, fy, cx, cy, baseline), one for all frames or one per frame.  Status as in `visual_stereo.STATUS`.
 
-Out of scope: unrectified pairs, different principal points, pyramids, speckle and median post-filters.
+Raw (distorted, unrectified) pairs enter through rectify.py's `keyframe_clouds_stereo_raw`.
+
+Out of scope: different principal points, pyramids, speckle and median post-filters.
 
 There is no CPU path: without the library or a GPU the functions raise CslamHipError.
 """
@@ -34,12 +36,20 @@ class _Pairs:
     """A list of stereo frames on the device: both sides as given (1 or 3 channels each) and the cameras."""
 
     def __init__(self, ls, rs, cam, dev):
-        self.b = _Batch([i.shape for i in ls], dev)
-        self.l_off, self.r_off, self.cam = offsets([i.size for i in ls]), offsets([i.size for i in rs]), np.ascontiguousarray(cam)
-        self.t_left, self.t_lo = self.b.flat(ls, np.uint8, dev), to_dev(self.l_off, dev)
-        self.t_right, self.t_ro = self.b.flat(rs, np.uint8, dev), to_dev(self.r_off, dev)
-        self.t_cam = to_dev(self.cam, dev)
-        self.dev = dev
+        self.place(_Batch([i.shape for i in ls], dev), offsets([i.size for i in ls]), offsets([i.size for i in rs]), cam, dev)
+        self.t_left, self.t_right = self.b.flat(ls, np.uint8, dev), self.b.flat(rs, np.uint8, dev)
+
+    def place(self, b, l_off, r_off, cam, dev):
+        self.b, self.l_off, self.r_off, self.cam, self.dev = b, l_off, r_off, np.ascontiguousarray(cam), dev
+        self.t_lo, self.t_ro, self.t_cam = to_dev(l_off, dev), to_dev(r_off, dev), to_dev(self.cam, dev)
+
+    @classmethod
+    def on_device(cls, b, t_left, l_off, t_right, r_off, cam, dev):
+        """Pairs whose bytes are on the device already (front_end/rectify.py chains into the functions below)."""
+        p = cls.__new__(cls)
+        p.place(b, l_off, r_off, cam, dev)
+        p.t_left, p.t_right = t_left, t_right
+        return p
 
 
 def _gray(lib, p, t_src, t_so, src_off):
@@ -71,6 +81,22 @@ def _by_left_channels(ls):
     for k, i in enumerate(ls):
         g.setdefault(3 if i.ndim == 3 else 1, []).append(k)
     return g
+
+
+def _clouds(lib, p, channels, params, v, r):
+    """The clouds of the pairs `p`, whose left images have `channels` channels: organised for v <= 0, else the chain
+    (`cslam_cloud_keyframes_stereo_dev`), a cloud that overflowed its voxel grid as None."""
+    if v <= 0.0:
+        f = _Frames.on_device(p.b, p.t_left, _dense(lib, p, params, False)[2], to_dev(p.cam[:, :4], p.dev), (CLOUD_DEPTH_F32, channels))
+        return _organised(f, *_project(lib, f))
+    b = p.b
+    t_out, lay = result_buffer(b.n, b.total, 4, p.dev)
+    _lib.check(lib.cslam_cloud_keyframes_stereo_dev(p.t_left.data_ptr(), p.t_lo.data_ptr(), channels, p.t_right.data_ptr(),
+                                                    p.t_ro.data_ptr(), b.t_off.data_ptr(), b.t_hw.data_ptr(), p.t_cam.data_ptr(), b.n,
+                                                    *params, v, r, *result_args(t_out, lay), host(p.l_off), host(p.r_off), host(b.off),
+                                                    host(b.hw), host(p.cam), stream()))
+    res, bad = unpack_result(t_out.cpu().numpy(), lay, b.n, np.float32)
+    return [None if c in bad else x for c, x in enumerate(res)]
 
 
 # ---- public ----------------------------------------------------------------------------------------------------------
@@ -114,25 +140,11 @@ def keyframe_clouds_stereo(lefts, rights, cameras, voxel_size=0.05, max_range=2.
     params = _parameters(min_disparity, max_disparity, uniqueness, lr_tolerance)
     cam = _stereo_cameras(cameras, len(ls))
 
-    def organised(lib, p, channels):
-        f = _Frames.on_device(p.b, p.t_left, _dense(lib, p, params, False)[2], to_dev(p.cam[:, :4], p.dev), (CLOUD_DEPTH_F32, channels))
-        return _organised(f, *_project(lib, f))
-
-    def chain(lib, p, channels):
-        b = p.b
-        t_out, lay = result_buffer(b.n, b.total, 4, p.dev)
-        _lib.check(lib.cslam_cloud_keyframes_stereo_dev(p.t_left.data_ptr(), p.t_lo.data_ptr(), channels, p.t_right.data_ptr(),
-                                                        p.t_ro.data_ptr(), b.t_off.data_ptr(), b.t_hw.data_ptr(), p.t_cam.data_ptr(), b.n,
-                                                        *params, v, r, *result_args(t_out, lay), host(p.l_off), host(p.r_off), host(b.off),
-                                                        host(b.hw), host(p.cam), stream()))
-        res, bad = unpack_result(t_out.cpu().numpy(), lay, b.n, np.float32)
-        return [None if c in bad else x for c, x in enumerate(res)]
-
     out = [None] * len(ls)
     with gpu(device) as (lib, dev):
         for channels, sel in _by_left_channels(ls).items():
             p = _Pairs([ls[k] for k in sel], [rs[k] for k in sel], cam[sel], dev)
-            for k, x in zip(sel, (organised if v <= 0.0 else chain)(lib, p, channels)):
+            for k, x in zip(sel, _clouds(lib, p, channels, params, v, r)):
                 out[k] = x
     failed = [k for k, x in enumerate(out) if x is None]
     if failed:

@@ -270,26 +270,34 @@ def extract_features(images, depths, cameras, max_features=1000, quality_level=0
     mf, q, md, bd = _selection(max_features, quality_level, min_distance, border, [i.shape for i in imgs])
     cam = _cameras(cameras, len(imgs))
     with gpu(device) as (lib, dev):
-        import torch
         if not imgs:
             return []
         b = _Batch([i.shape for i in imgs], dev)
         src_off = offsets([i.size for i in imgs])
-        t_src, t_so, t_depth, t_cam = b.flat(imgs, np.uint8, dev), to_dev(src_off, dev), b.flat(dps, np.float32, dev), to_dev(cam, dev)
-        t_cnt = torch.zeros(b.n, dtype=torch.int32, device=dev)
-        t_kp = torch.zeros((b.n, mf, 2), dtype=torch.int32, device=dev)
-        t_resp = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
-        t_bins = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
-        t_desc = torch.zeros((b.n, mf, FEAT_DESC_BYTES), dtype=torch.uint8, device=dev)
-        t_pts = torch.zeros((b.n, mf, 3), dtype=torch.float64, device=dev)
-        _lib.check(lib.cslam_feat_extract_dev(t_src.data_ptr(), t_so.data_ptr(), t_depth.data_ptr(), b.t_off.data_ptr(), b.t_hw.data_ptr(),
-                                              t_cam.data_ptr(), b.n, q, md, bd, mf, 1 if depth_as_mask else 0, t_cnt.data_ptr(), t_kp.data_ptr(),
-                                              t_resp.data_ptr(), t_bins.data_ptr(), t_desc.data_ptr(), t_pts.data_ptr(), host(src_off),
-                                              host(b.off), host(b.hw), stream()))
-        cnt = t_cnt.cpu().numpy()
-        kp, resp, bins, desc, pts = (t.cpu().numpy() for t in (t_kp, t_resp, t_bins, t_desc, t_pts))
+        return _extract_on_device(lib, dev, b, b.flat(imgs, np.uint8, dev), to_dev(src_off, dev), src_off, b.flat(dps, np.float32, dev), cam,
+                                  (mf, q, md, bd), depth_as_mask)
+
+
+def _extract_on_device(lib, dev, b, t_src, t_so, src_off, t_depth, cam, selection, depth_as_mask):
+    """`cslam_feat_extract_dev` on images and depths that are on the device already (front_end/rectify.py chains into it), and
+    the one download: the list `extract_features` returns."""
+    import torch
+    mf, q, md, bd = selection
+    t_cam = to_dev(cam, dev)
+    t_cnt = torch.zeros(b.n, dtype=torch.int32, device=dev)
+    t_kp = torch.zeros((b.n, mf, 2), dtype=torch.int32, device=dev)
+    t_resp = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
+    t_bins = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
+    t_desc = torch.zeros((b.n, mf, FEAT_DESC_BYTES), dtype=torch.uint8, device=dev)
+    t_pts = torch.zeros((b.n, mf, 3), dtype=torch.float64, device=dev)
+    _lib.check(lib.cslam_feat_extract_dev(t_src.data_ptr(), t_so.data_ptr(), t_depth.data_ptr(), b.t_off.data_ptr(), b.t_hw.data_ptr(),
+                                          t_cam.data_ptr(), b.n, q, md, bd, mf, 1 if depth_as_mask else 0, t_cnt.data_ptr(), t_kp.data_ptr(),
+                                          t_resp.data_ptr(), t_bins.data_ptr(), t_desc.data_ptr(), t_pts.data_ptr(), host(src_off),
+                                          host(b.off), host(b.hw), stream()))
+    cnt = t_cnt.cpu().numpy()
+    kp, resp, bins, desc, pts = (t.cpu().numpy() for t in (t_kp, t_resp, t_bins, t_desc, t_pts))
     return [dict(keypoints=kp[c, :cnt[c]].copy(), responses=resp[c, :cnt[c]].copy(), bins=bins[c, :cnt[c]].copy(),
-                 descriptors=desc[c, :cnt[c]].copy(), points=pts[c, :cnt[c]].copy()) for c in range(len(imgs))]
+                 descriptors=desc[c, :cnt[c]].copy(), points=pts[c, :cnt[c]].copy()) for c in range(b.n)]
 
 
 def extract_keyframes(images, depths, cameras, max_features=1000, quality_level=0.001, min_distance=7, border=19, depth_as_mask=True, device=0):

@@ -10,9 +10,10 @@ tests/stereo_reference.py restates, and the two agree bit for bit.
 
 Images are uint8, the two sides of a frame of the same H x W; a camera is (fx, fy, cx, cy, baseline), baseline in metres,
 one for all frames or one per frame.  Status: 0 accepted, 1 outside, 2 no range, 3 edge, 4 not unique, 5 left-right.
+Raw (distorted, unrectified) pairs enter through rectify.py's `extract_keyframes_stereo_raw`.
 
-Out of scope: unrectified pairs, different principal points, a pyramid inside the correspondence search (the keypoints' scale
-pyramid is visual_pyramid.py's), rtabmap's optical-flow variant, Vis/MinDepth and Vis/MaxDepth.
+Out of scope: different principal points, a pyramid inside the correspondence search (the keypoints' scale pyramid is
+visual_pyramid.py's), rtabmap's optical-flow variant, Vis/MinDepth and Vis/MaxDepth.
 
 There is no CPU path: without the library or a GPU the functions raise CslamHipError.
 """
@@ -128,31 +129,39 @@ def extract_features_stereo(lefts, rights, cameras, max_features=1000, quality_l
     lo, hi, uq, lr = _parameters(min_disparity, max_disparity, uniqueness, lr_tolerance)
     cam = _stereo_cameras(cameras, len(ls))
     with gpu(device) as (lib, dev):
-        import torch
         if not ls:
             return []
         b = _Batch([i.shape for i in ls], dev)
         l_off, r_off = offsets([i.size for i in ls]), offsets([i.size for i in rs])
-        t_left, t_lo, t_right, t_ro = b.flat(ls, np.uint8, dev), to_dev(l_off, dev), b.flat(rs, np.uint8, dev), to_dev(r_off, dev)
-        t_cam = to_dev(cam, dev)
-        t_cnt = torch.zeros(b.n, dtype=torch.int32, device=dev)
-        t_kp = torch.zeros((b.n, mf, 2), dtype=torch.int32, device=dev)
-        t_resp = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
-        t_bins = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
-        t_desc = torch.zeros((b.n, mf, FEAT_DESC_BYTES), dtype=torch.uint8, device=dev)
-        t_pts = torch.zeros((b.n, mf, 3), dtype=torch.float64, device=dev)
-        t_disp = torch.zeros((b.n, mf), dtype=torch.float64, device=dev)
-        t_status = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
-        _lib.check(lib.cslam_feat_extract_stereo_dev(t_left.data_ptr(), t_lo.data_ptr(), t_right.data_ptr(), t_ro.data_ptr(), b.t_off.data_ptr(),
-                                                     b.t_hw.data_ptr(), t_cam.data_ptr(), b.n, q, md, bd, mf, lo, hi, uq, lr, t_cnt.data_ptr(),
-                                                     t_kp.data_ptr(), t_resp.data_ptr(), t_bins.data_ptr(), t_desc.data_ptr(), t_pts.data_ptr(),
-                                                     t_disp.data_ptr(), t_status.data_ptr(), host(l_off), host(r_off), host(b.off), host(b.hw),
-                                                     host(cam), stream()))
-        cnt = t_cnt.cpu().numpy()
-        kp, resp, bins, desc, pts, disp, status = (t.cpu().numpy() for t in (t_kp, t_resp, t_bins, t_desc, t_pts, t_disp, t_status))
+        return _extract_stereo_on_device(lib, dev, b, b.flat(ls, np.uint8, dev), to_dev(l_off, dev), l_off, b.flat(rs, np.uint8, dev),
+                                         to_dev(r_off, dev), r_off, cam, (mf, q, md, bd), (lo, hi, uq, lr))
+
+
+def _extract_stereo_on_device(lib, dev, b, t_left, t_lo, l_off, t_right, t_ro, r_off, cam, selection, parameters):
+    """`cslam_feat_extract_stereo_dev` on pairs that are on the device already (front_end/rectify.py chains into it), and the one
+    download: the list `extract_features_stereo` returns."""
+    import torch
+    mf, q, md, bd = selection
+    lo, hi, uq, lr = parameters
+    t_cam = to_dev(cam, dev)
+    t_cnt = torch.zeros(b.n, dtype=torch.int32, device=dev)
+    t_kp = torch.zeros((b.n, mf, 2), dtype=torch.int32, device=dev)
+    t_resp = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
+    t_bins = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
+    t_desc = torch.zeros((b.n, mf, FEAT_DESC_BYTES), dtype=torch.uint8, device=dev)
+    t_pts = torch.zeros((b.n, mf, 3), dtype=torch.float64, device=dev)
+    t_disp = torch.zeros((b.n, mf), dtype=torch.float64, device=dev)
+    t_status = torch.zeros((b.n, mf), dtype=torch.int32, device=dev)
+    _lib.check(lib.cslam_feat_extract_stereo_dev(t_left.data_ptr(), t_lo.data_ptr(), t_right.data_ptr(), t_ro.data_ptr(), b.t_off.data_ptr(),
+                                                 b.t_hw.data_ptr(), t_cam.data_ptr(), b.n, q, md, bd, mf, lo, hi, uq, lr, t_cnt.data_ptr(),
+                                                 t_kp.data_ptr(), t_resp.data_ptr(), t_bins.data_ptr(), t_desc.data_ptr(), t_pts.data_ptr(),
+                                                 t_disp.data_ptr(), t_status.data_ptr(), host(l_off), host(r_off), host(b.off), host(b.hw),
+                                                 host(cam), stream()))
+    cnt = t_cnt.cpu().numpy()
+    kp, resp, bins, desc, pts, disp, status = (t.cpu().numpy() for t in (t_kp, t_resp, t_bins, t_desc, t_pts, t_disp, t_status))
     return [dict(keypoints=kp[c, :cnt[c]].copy(), responses=resp[c, :cnt[c]].copy(), bins=bins[c, :cnt[c]].copy(),
                  descriptors=desc[c, :cnt[c]].copy(), points=pts[c, :cnt[c]].copy(), disparity=disp[c, :cnt[c]].copy(),
-                 status=status[c, :cnt[c]].copy()) for c in range(len(ls))]
+                 status=status[c, :cnt[c]].copy()) for c in range(b.n)]
 
 
 def extract_keyframes_stereo(lefts, rights, cameras, max_features=1000, quality_level=0.001, min_distance=7, border=19, min_disparity=1,

@@ -851,9 +851,9 @@ int cslam_feat_extract_dev(const uint8_t *d_src, const int64_t *d_src_off, const
  * Point (status 0, otherwise a NaN row): Z = (baseline fx) / disparity, X = ((u - cx) Z) / fx, Y = ((v - cy) Z) / fy.
  * Diagnostic: best int32 [rows, 4] = (d*, a, b, c); d* = -1 for status 1 and 2; each of a, b, c is -1 where that disparity
  *   lies outside [D_lo, D_hi].
- * Out of scope: unrectified pairs, different principal points in the two images, a pyramid inside the correspondence search
- *   (the keypoints' scale pyramid: the next section), rtabmap's optical-flow variant
- *   of the correspondence search, Vis/MinDepth and Vis/MaxDepth. */
+ * Raw pairs are rectified by the raw-camera section below.  Out of scope: different principal points in the two images, a
+ *   pyramid inside the correspondence search (the keypoints' scale pyramid: the next section), rtabmap's optical-flow
+ *   variant of the correspondence search, Vis/MinDepth and Vis/MaxDepth. */
 /* cslam_feat_stereo_dev -- the depth of generateKeypoints3D (rgbd_handler.cpp:309) for a stereo frame
  *   (stereo_handler.cpp:148-227): d_left, d_right uint8 [total pixels] grey in the ragged layout of the feature section
  *   (d_off, d_hw, h_off, h_hw), keypoints d_kp int32 [total, 2] with d_kp_off int64 [n + 1] (h_kp_off: the same on the
@@ -1010,7 +1010,8 @@ int cslam_feat_extract_stereo_pyramid_subpix_dev(const uint8_t *d_left, const in
  * pixel, for every admitted parameter value; tests/stereo_dense_reference.py restates the dense form in numpy (cost slab by
  * prefix sums, one back search per right pixel, the rival among the four smallest keys) and agrees bit for bit.  Unpinned:
  * parity with rtabmap's or OpenCV's dense matchers (StereoBM / StereoSGBM).
- * Out of scope: unrectified pairs, different principal points, pyramids, speckle and median post-filters.
+ * Raw pairs are rectified by the section below.  Out of scope: different principal points, pyramids, speckle and median
+ * post-filters.
  *
  * cslam_stereo_dense_dev -- d_left, d_right uint8 grey [total pixels] in the ragged layout of the feature section, d_cameras
  *   float64 [n, 5] (h_cameras required), parameters as cslam_feat_stereo_dev, whose argument checks these are, all before any
@@ -1034,6 +1035,52 @@ int cslam_cloud_keyframes_stereo_dev(const uint8_t *d_left, const int64_t *d_lef
                                      double max_range, float *d_out, uint32_t *d_out_rgb, int32_t *d_counts, int64_t *d_out_offsets,
                                      int32_t *d_status, const int64_t *h_left_off, const int64_t *h_right_off, const int64_t *h_off,
                                      const int32_t *h_hw, const double *h_cameras, void *stream);
+
+/* ------------------------------------------------------------------------------------------------
+ * Raw cameras: undistort and rectify images and depth (csrc/rectify.hip, the rule csrc/rectify.h's).  Replaces image_proc's
+ * and stereo_image_proc's rectify in front of the reference, that is OpenCV initUndistortRectifyMap + remap
+ * (stereo_handler.cpp:120 hard-codes alreadyRectified = true): the step between a camera driver's frame with its
+ * CameraInfo and every visual stage above.
+ * A raw camera is 26 float64: K = (fx, fy, cx, cy), D = (k1, k2, p1, p2, k3, k4, k5, k6), R row-major 3 x 3,
+ * P = (fx', fy', cx', cy') and P[0][3] = Tx fx', which the map ignores.  The rule, in float64 with every operation rounded
+ * on its own: x = (u - cx') / fx', y = (v - cy') / fy', (X, Y, Wd) = R^T (x, y, 1), outside unless Wd > 0, xn = X / Wd,
+ * yn = Y / Wd, r2 = xn xn + yn yn, rad = (1 + k1 r2 + k2 r4 + k3 r6) / (1 + k4 r2 + k5 r4 + k6 r6),
+ * xd = xn rad + 2 p1 xn yn + p2 (r2 + 2 xn xn), yd = yn rad + p1 (r2 + 2 yn yn) + 2 p2 xn yn, m = (fx xd + cx, fy yd + cy),
+ * q = floor(32 m + 0.5) as int32, both INT32_MIN when outside, not finite or |q| >= 2^26.
+ * Pinned: tests/rectify_reference.py restates map, bilinear and nearest sampling in numpy and agrees bit for bit.
+ * Unpinned: parity with OpenCV / image_proc (fixed-point tables, border handling), which were not available to compare.
+ * Out of scope: different principal points of the two sides, computing R and P from an extrinsic calibration (Bouguet;
+ * CameraInfo carries them), fisheye / equidistant models.
+ *
+ * cslam_rectify_map_dev -- d_cameras float64 [n, 26] (h_cameras required: finite, positive focal lengths, R orthonormal to
+ *   1e-9 with positive determinant), destination sizes d_hw / d_off in the ragged layout of the feature section ->
+ *   d_map int32 [total, 2] = (qx, qy).  A thread per pixel, no atomics.
+ * cslam_rectify_remap_dev -- n frames; frame c reads d_src + d_src_off[c] (uint8, d_src_hw[c] = (Hs, Ws), 1 channel or 3
+ *   interleaved by its length), goes through map d_map_index[c] of the n_maps maps at d_map_off (pixels; the map's size is
+ *   the frame's d_hw[c]) and writes its channels at d_dst + d_dst_off[c] (bytes) and d_valid uint8 [total] at d_off[c].
+ *   Bilinear on the 1/32 grid: x0 = qx >> 5, ax = qx & 31, weights (32 - ax)(32 - ay), ..., a tap outside contributes 0,
+ *   value = (sum + 512) >> 10, valid = 1 iff every tap of non-zero weight lies inside.  A frame's bytes are the same alone, in
+ *   any batch and in any order.
+ * cslam_rectify_nearest_dev -- the same for depth, never interpolated: src_type CSLAM_RECTIFY_U16 or CSLAM_RECTIFY_F32,
+ *   offsets in elements, the element at ((qx + 16) >> 5, (qy + 16) >> 5) with its bits preserved, 0 outside; d_dst in the
+ *   layout of d_off.  d_mask uint8 [total] may be NULL; where it is 0 the output is 0 (the validity of the colour image,
+ *   so that the depth mask of cslam_feat_extract_dev drops what the image does not cover).
+ * All host copies are required, every check precedes the launch, everything is enqueued on `stream`. */
+#define CSLAM_RECTIFY_U16 0
+#define CSLAM_RECTIFY_F32 1
+int cslam_rectify_map_dev(const double *d_cameras, const int64_t *d_off, const int32_t *d_hw, int n, int32_t *d_map,
+                          const int64_t *h_off, const int32_t *h_hw, const double *h_cameras, void *stream);
+int cslam_rectify_remap_dev(const uint8_t *d_src, const int64_t *d_src_off, const int32_t *d_src_hw, const int32_t *d_map,
+                            const int64_t *d_map_off, const int32_t *d_map_index, int n_maps, const int64_t *d_off,
+                            const int32_t *d_hw, int n, uint8_t *d_dst, const int64_t *d_dst_off, uint8_t *d_valid,
+                            const int64_t *h_src_off, const int32_t *h_src_hw, const int64_t *h_map_off, const int32_t *h_map_hw,
+                            const int32_t *h_map_index, const int64_t *h_off, const int32_t *h_hw, const int64_t *h_dst_off,
+                            void *stream);
+int cslam_rectify_nearest_dev(const void *d_src, int src_type, const int64_t *d_src_off, const int32_t *d_src_hw,
+                              const int32_t *d_map, const int64_t *d_map_off, const int32_t *d_map_index, int n_maps,
+                              const int64_t *d_off, const int32_t *d_hw, int n, const uint8_t *d_mask, void *d_dst,
+                              const int64_t *h_src_off, const int32_t *h_src_hw, const int64_t *h_map_off, const int32_t *h_map_hw,
+                              const int32_t *h_map_index, const int64_t *h_off, const int32_t *h_hw, void *stream);
 
 /* Winograd F(2x2, 3x3) transforms for the 3x3 / stride 1 / pad 1 convolutions of the extractor backbone
  * (the VGG-16 trunk built at cslam/vpr/netvlad.py:163-171; the reference runs it through torch's direct

@@ -148,6 +148,8 @@ _SIGNATURES = {
                                       _vp, _vp, _vp]),
     "cslam_vis_register_levels_dev": (_i, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i, _i, C.c_double, _i, C.c_double, _i, _i, _i, C.c_uint64,
                                            _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "cslam_vis_ba_dev": (_i, [_vp] * 17 + [_i, C.c_double, _i, _i, _i] + [_vp] * 12),
+    "cslam_vis_register_ba_dev": (_i, [_vp] * 13 + [_i, _i, C.c_double, _i, C.c_double, _i, _i, _i, C.c_uint64, _i, _i] + [_vp] * 16),
     "cslam_vis_hypotheses_dev": (_i, [_vp, _vp, _vp, _vp, _i, _i, C.c_double, C.c_uint64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "cslam_feat_gray_dev": (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),
     "cslam_feat_response_dev": (_i, [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _vp]),

@@ -17,6 +17,12 @@ correspondence whose "to" keypoint has level l is an inlier iff its depth is pos
 <= reproj_error^2 sigma2[l], and its Gauss-Newton terms are multiplied by 1 / sigma2[l]; everything else is the rule above
 (tests/vis_levels_reference.py restates it).  Parity with rtabmap's use of cv::KeyPoint::octave is unpinned too.
 
+The adjusted forms (`register_pairs_ba`, `compute_transformation_ba`, `bundle_adjust_pairs`; csrc/vis_ba.hip, csrc/ba.h) follow
+the PnP fit with a two-view bundle adjustment, as rtabmap's computeTransformation does at its defaults: the transform and one
+point per inlier are refined against the keypoints and depths of BOTH keyframes (include/cslam_hip.h states the rule,
+tests/vis_ba_reference.py restates it).  Parity with rtabmap's g2o adjustment is unpinned like the rest, and the default
+baseline of 0.1 m that weighs a depth against a pixel is this library's own choice.
+
 There is no CPU path: without the library or a GPU the functions raise CslamHipError.
 """
 from collections import namedtuple
@@ -337,3 +343,205 @@ def compute_transformation(kf_from, kf_to, camera, **kwargs):
 def compute_level_transformation(kf_from, kf_to, camera, **kwargs):
     """The one-pair form of `register_level_pairs`."""
     return register_level_pairs([(kf_from, kf_to)], camera, **kwargs)[0]
+
+
+# ---- two-view bundle adjustment after PnP (csrc/vis_ba.hip, csrc/ba.h) ------------------------------------------------
+class RefinedRegistration(VisualRegistration):
+    """A `VisualRegistration` after the two-view bundle adjustment (`to_edge` works as before): `transformation`, `status`
+    and `inliers` are the adjustment's (a PnP status other than 0 passes through untouched); also `pnp` (the registration
+    before), `points` [K, 3] (the refined point of every final inlier in the "from" camera frame, NaN elsewhere),
+    `cost_before`, `cost_after` (the weighted cost at the PnP fit and the one the last round ended with; NaN where nothing
+    was adjusted), `set_in`, `ba_steps`, `rounds_discarded`, `points_held`."""
+
+    def __init__(self, pnp, transformation, status, inliers, points, cost_before, cost_after, set_in, ba_steps, rounds_discarded, points_held):
+        super().__init__(transformation, status == 0, status, pnp.matches, inliers, pnp.dropped_no_depth, pnp.best_hypothesis)
+        self.pnp = pnp
+        self.points = points
+        self.cost_before, self.cost_after = cost_before, cost_after
+        self.set_in, self.ba_steps, self.rounds_discarded, self.points_held = set_in, ba_steps, rounds_discarded, points_held
+
+    def __repr__(self):
+        return "RefinedRegistration(status=%d, inliers=%d of %d adjusted, steps=%d, cost %.6g -> %.6g; before: %r)" % (
+            self.status, int(np.count_nonzero(self.inliers)), self.set_in, self.ba_steps, self.cost_before, self.cost_after, self.pnp)
+
+
+def _baselines(baselines, n):
+    b = np.asarray(baselines, dtype=np.float64)
+    if b.ndim == 0:
+        b = np.full((n, 2), float(b))
+    elif b.shape == (2,):
+        b = np.repeat(b[None], n, axis=0)
+    if b.shape != (n, 2):
+        raise ValueError("baselines are one number, (from, to), or one (from, to) per pair: got shape %s for %d pairs" % (b.shape, n))
+    if not (np.all(np.isfinite(b)) and np.all(b > 0.0)):
+        raise ValueError("baselines must be positive and finite")
+    return np.ascontiguousarray(b)
+
+
+def _ba_settings(ba_iterations, ba_rounds):
+    bi, br = int(ba_iterations), int(ba_rounds)
+    if bi < 0 or br < 0:
+        raise ValueError("ba_iterations and ba_rounds must not be negative")
+    return bi, br
+
+
+def _ba_keyframes(pairs_of_keyframes):
+    """Per pair ((kp, pts, desc, levels or None) of "from", the same of "to"); levels are kept only where both carry them."""
+    out = []
+    for a, b in pairs_of_keyframes:
+        both = hasattr(a, "levels") and hasattr(b, "levels")
+        ka, kb = (_level_keyframe(a), _level_keyframe(b)) if both else (_keyframe(a) + (None,), _keyframe(b) + (None,))
+        out.append((ka, kb))
+    return out
+
+
+def _by_form(kfs):
+    """The indices of the pairs with levels and of those without: each group is one call, so that a pair's bytes do not depend
+    on what else the batch holds."""
+    with_levels = [p for p, (a, _) in enumerate(kfs) if a[3] is not None]
+    return [g for g in (with_levels, [p for p in range(len(kfs)) if kfs[p][0][3] is None]) if g]
+
+
+def _ba_uploads(kfs, cam_a, cam_b, base, dev):
+    a_off, b_off = offsets([len(a[0]) for a, _ in kfs]), offsets([len(b[0]) for _, b in kfs])
+    t = dict(kp_a=to_dev(_cat([a[0] for a, _ in kfs], 2, np.float64), dev), pts_a=to_dev(_cat([a[1] for a, _ in kfs], 3, np.float64), dev),
+             kp_b=to_dev(_cat([b[0] for _, b in kfs], 2, np.float64), dev), pts_b=to_dev(_cat([b[1] for _, b in kfs], 3, np.float64), dev),
+             a_off=to_dev(a_off, dev), b_off=to_dev(b_off, dev), cam_a=to_dev(cam_a, dev), cam_b=to_dev(cam_b, dev), base=to_dev(base, dev))
+    h_la = h_lb = None
+    if kfs[0][0][3] is not None:
+        h_la = np.concatenate([a[3] for a, _ in kfs]) if int(a_off[-1]) else np.zeros(1, dtype=np.int32)
+        h_lb = np.concatenate([b[3] for _, b in kfs]) if int(b_off[-1]) else np.zeros(1, dtype=np.int32)
+        t["la"], t["lb"] = to_dev(h_la, dev), to_dev(h_lb, dev)
+    return t, a_off, b_off, h_la, h_lb
+
+
+def _ba_outputs(n, total, dev):
+    import torch
+    return (_outputs(n, total, dev) + (torch.zeros((max(total, 1), 3), dtype=torch.float64, device=dev),
+                                       torch.zeros((n, 2), dtype=torch.float64, device=dev)))
+
+
+def _refined(pnp, T, info, flags, points, cost, off):
+    out = []
+    for p, reg in enumerate(pnp):
+        k = len(reg.matches)
+        out.append(RefinedRegistration(reg, T[p].reshape(4, 4).copy(), int(info[p, 0]), flags[off[p]:off[p] + k].astype(bool),
+                                       points[off[p]:off[p] + k].copy(), float(cost[p, 0]), float(cost[p, 1]), int(info[p, 1]),
+                                       int(info[p, 3]), int(info[p, 4]), int(info[p, 5])))
+    return out
+
+
+def _ptr(t, key):
+    return t[key].data_ptr() if key in t else None
+
+
+def _adjust_group(kfs, regs, cam_a, cam_b, base, e, mi, bi, br, lib, dev):
+    n = len(kfs)
+    t, a_off, b_off, h_la, h_lb = _ba_uploads(kfs, cam_a, cam_b, base, dev)
+    rows = [np.ascontiguousarray(r.matches, dtype=np.int32).reshape(-1, 2) for r in regs]
+    r_off = offsets([len(r) for r in rows])
+    total = int(r_off[-1])
+    h_rows = _cat(rows, 2, np.int32) if total else np.zeros((1, 2), dtype=np.int32)
+    h_flags = np.concatenate([np.asarray(r.inliers).astype(np.int32) for r in regs]) if total else np.zeros(1, dtype=np.int32)
+    h_T0 = np.stack([np.asarray(r.transformation, dtype=np.float64).reshape(16) for r in regs])
+    h_info0 = np.zeros((n, 8), dtype=np.int32)
+    for p, r in enumerate(regs):
+        h_info0[p] = (r.status, len(r.matches), len(r.matches) - r.dropped_no_depth, r.dropped_no_depth, int(np.count_nonzero(r.inliers)),
+                      r.best_hypothesis, 0, 0)
+    t_rows, t_roff, t_f0, t_T0, t_i0 = (to_dev(x, dev) for x in (h_rows, r_off, h_flags, h_T0, h_info0))
+    t_T, t_info, t_flags, t_pts, t_cost = _ba_outputs(n, total, dev)
+    _lib.check(lib.cslam_vis_ba_dev(t["kp_a"].data_ptr(), t["pts_a"].data_ptr(), t["a_off"].data_ptr(), t["kp_b"].data_ptr(),
+                                    t["pts_b"].data_ptr(), t["b_off"].data_ptr(), _ptr(t, "la"), _ptr(t, "lb"), t["cam_a"].data_ptr(),
+                                    t["cam_b"].data_ptr(), t["base"].data_ptr(), t_rows.data_ptr(), t_roff.data_ptr(), None,
+                                    t_T0.data_ptr(), t_i0.data_ptr(), t_f0.data_ptr(), n, e, mi, bi, br, t_T.data_ptr(), t_info.data_ptr(),
+                                    t_flags.data_ptr(), t_pts.data_ptr(), t_cost.data_ptr(), host(a_off), host(b_off), host(r_off),
+                                    None if h_la is None else host(h_la), None if h_lb is None else host(h_lb), host(base), stream()))
+    return _refined(regs, t_T.cpu().numpy(), t_info.cpu().numpy(), t_flags.cpu().numpy(), t_pts.cpu().numpy(), t_cost.cpu().numpy(), r_off)
+
+
+def bundle_adjust_pairs(pairs_of_keyframes, registrations, cameras_from, cameras_to=None, baselines=0.1, reproj_error=2.0, min_inliers=20,
+                        ba_iterations=10, ba_rounds=2, device=0):
+    """The staged form (`cslam_vis_ba_dev`): the two-view bundle adjustment of include/cslam_hip.h on a list of
+    (keyframe_from, keyframe_to) and the `VisualRegistration` PnP gave for each (its `matches`, `inliers`, `transformation`
+    and `status`).  `Keyframe` or `LevelKeyframe`; the levels weigh the residuals where both keyframes of a pair carry them.
+    `cameras_from` / `cameras_to` (None: the same): (fx, fy, cx, cy), one for all or one per pair.  `baselines`: metres, one
+    number, (from, to), or one (from, to) per pair; the depth weight of a view is fx * baseline: the real baseline of a
+    stereo camera, a virtual one for RGB-D.  The default 0.1 m is this library's own choice; parity with rtabmap's value is
+    unpinned.  Returns a `RefinedRegistration` per pair."""
+    e, mi = float(reproj_error), int(min_inliers)
+    if not (np.isfinite(e) and e > 0.0):
+        raise ValueError("reproj_error must be positive and finite")
+    if mi < 1:
+        raise ValueError("min_inliers must be at least 1")
+    bi, br = _ba_settings(ba_iterations, ba_rounds)
+    kfs = _ba_keyframes(pairs_of_keyframes)
+    regs = list(registrations)
+    if len(regs) != len(kfs):
+        raise ValueError("one registration per pair of keyframes: %d and %d" % (len(regs), len(kfs)))
+    for r in regs:
+        m = np.asarray(r.matches)
+        if m.ndim != 2 or m.shape[1] != 2 or len(r.inliers) != len(m) or np.asarray(r.transformation).shape != (4, 4):
+            raise ValueError("a registration carries matches [K, 2], inliers [K] and a 4 x 4 transformation")
+    cam_a = _cameras(cameras_from, len(kfs))
+    cam_b = cam_a if cameras_to is None else _cameras(cameras_to, len(kfs))
+    base = _baselines(baselines, len(kfs))
+    out = [None] * len(kfs)
+    with gpu(device) as (lib, dev):
+        for g in _by_form(kfs):
+            res = _adjust_group([kfs[p] for p in g], [regs[p] for p in g], cam_a[g], cam_b[g], base[g], e, mi, bi, br, lib, dev)
+            for p, r in zip(g, res):
+                out[p] = r
+    return out
+
+
+def _register_ba_group(kfs, cam_a, cam_b, base, r, it, e, mi, ri, rr, sd, bi, br, lib, dev):
+    import torch
+    n = len(kfs)
+    t, a_off, b_off, h_la, h_lb = _ba_uploads(kfs, cam_a, cam_b, base, dev)
+    t_da = to_dev(_cat([a[2] for a, _ in kfs], 32, np.uint8), dev)
+    t_db = to_dev(_cat([b[2] for _, b in kfs], 32, np.uint8), dev)
+    total = int(a_off[-1])
+    t_rows = torch.zeros((max(total, 1), 2), dtype=torch.int32, device=dev)
+    t_cnt = torch.zeros(n, dtype=torch.int32, device=dev)
+    t_T0, t_i0, t_f0 = _outputs(n, total, dev)
+    t_T, t_info, t_flags, t_pts, t_cost = _ba_outputs(n, total, dev)
+    _lib.check(lib.cslam_vis_register_ba_dev(t_da.data_ptr(), t["kp_a"].data_ptr(), t["pts_a"].data_ptr(), t["a_off"].data_ptr(),
+                                             t_db.data_ptr(), t["kp_b"].data_ptr(), t["pts_b"].data_ptr(), t["b_off"].data_ptr(),
+                                             _ptr(t, "la"), _ptr(t, "lb"), t["cam_a"].data_ptr(), t["cam_b"].data_ptr(), t["base"].data_ptr(),
+                                             n, VIS_DESC_BYTES, r, it, e, mi, ri, rr, sd, bi, br, t_rows.data_ptr(), t_cnt.data_ptr(),
+                                             t_T0.data_ptr(), t_i0.data_ptr(), t_f0.data_ptr(), t_T.data_ptr(), t_info.data_ptr(),
+                                             t_flags.data_ptr(), t_pts.data_ptr(), t_cost.data_ptr(), host(a_off), host(b_off),
+                                             None if h_la is None else host(h_la), None if h_lb is None else host(h_lb), host(base), stream()))
+    pnp = _registrations(t_T0.cpu().numpy(), t_i0.cpu().numpy(), t_f0.cpu().numpy(), t_rows.cpu().numpy(), a_off)
+    return _refined(pnp, t_T.cpu().numpy(), t_info.cpu().numpy(), t_flags.cpu().numpy(), t_pts.cpu().numpy(), t_cost.cpu().numpy(), a_off)
+
+
+def register_pairs_ba(pairs_of_keyframes, cameras_from, cameras_to=None, baselines=0.1, ba_iterations=10, ba_rounds=2, nndr=0.8,
+                      iterations=300, reproj_error=2.0, min_inliers=20, refine_iterations=10, refine_rounds=2, seed=0, device=0):
+    """Matching, PnP RANSAC and the two-view bundle adjustment of a list of (keyframe_from, keyframe_to) in ONE call per form
+    (`cslam_vis_register_ba_dev`), chained on the device with no host wait.  `Keyframe` or `LevelKeyframe`: a pair whose
+    keyframes both carry levels gets the level-aware PnP (`register_level_pairs`) and level weights in the adjustment, any
+    other pair the uniform PnP (`register_pairs`) and level 0; the two forms of a mixed batch are two calls.  PnP uses
+    `cameras_to` (None: `cameras_from`).  `baselines` as for `bundle_adjust_pairs`: the default 0.1 m is this library's own
+    choice and parity with rtabmap's value is unpinned.  Returns a `RefinedRegistration` per pair; its `pnp` equals what
+    `register_pairs` / `register_level_pairs` return for the pair."""
+    r = _nndr(nndr)
+    it, e, mi, ri, rr, sd = _ransac(iterations, reproj_error, min_inliers, refine_iterations, refine_rounds, seed)
+    bi, br = _ba_settings(ba_iterations, ba_rounds)
+    kfs = _ba_keyframes(pairs_of_keyframes)
+    cam_a = _cameras(cameras_from, len(kfs))
+    cam_b = cam_a if cameras_to is None else _cameras(cameras_to, len(kfs))
+    base = _baselines(baselines, len(kfs))
+    out = [None] * len(kfs)
+    with gpu(device) as (lib, dev):
+        for g in _by_form(kfs):
+            res = _register_ba_group([kfs[p] for p in g], cam_a[g], cam_b[g], base[g], r, it, e, mi, ri, rr, sd, bi, br, lib, dev)
+            for p, x in zip(g, res):
+                out[p] = x
+    return out
+
+
+def compute_transformation_ba(kf_from, kf_to, camera, **kwargs):
+    """The one-pair form of `register_pairs_ba`: what `registration_.computeTransformation(from, to, ...)` answers with its
+    bundle adjustment on."""
+    return register_pairs_ba([(kf_from, kf_to)], camera, **kwargs)[0]

@@ -740,6 +740,72 @@ int cslam_vis_register_levels_dev(const uint8_t *d_desc_from, const double *d_po
                                   int min_inliers, int refine_iterations, int refine_rounds, uint64_t seed, int32_t *d_rows,
                                   int32_t *d_count, double *d_T, int32_t *d_info, int32_t *d_flags, const int64_t *h_from_off,
                                   const int64_t *h_to_off, const int32_t *h_levels_to, void *stream);
+/* Two-view bundle adjustment after PnP (csrc/vis_ba.hip, csrc/ba.h; tests/vis_ba_reference.py restates it).  rtabmap's
+ *   computeTransformation, which rgbd_handler.cpp:443-445 and :519-520 call, follows its PnP at its defaults with a local bundle
+ *   adjustment over the two views; rtabmap and g2o are third party and were not available: parity with them is unpinned, and
+ *   what follows is this library's own rule.
+ *   Input per pair: keypoints [., 2], points [., 3] (camera frame), camera (fx, fy, cx, cy), baseline and optional levels of
+ *   both keyframes, the match rows, and what PnP wrote for them (T0, its info and flags).  The depth weight of a view is
+ *   w = fx * baseline: the real baseline of a stereo camera, a virtual one for RGB-D (the Python default 0.1 m is this
+ *   library's choice; parity with rtabmap's value is unpinned).
+ *   The adjusted set: the correspondences PnP flagged, in row order, whose rows lie inside their keyframes, whose two keypoints
+ *   and "from" X, Y are finite and whose "from" Z is finite and positive with a finite 1 / Z; a flagged row that is not
+ *   adjustable gets flag 0.  At most 2048; more (which no PnP status 0 of these entry points precedes): status 3, T0 and PnP's flags.
+ *   Unknowns: T = (R, t) from T0, and a point Y_k per member in the "from" camera frame, started at the "from" point.
+ *   Residuals of member k with levels la, lb and sigma2[l] = (double)36^l / (double)25^l:
+ *     view "from": (fx_a Yx / Yz + cx_a - u_a, fy_a Yy / Yz + cy_a - v_a, w_a (1 / Yz - 1 / Z_a)), squares weighted 1 / sigma2[la];
+ *     view "to":   the same of Q = R Y + t, the "to" keypoint, w_b and 1 / sigma2[lb]; the third component only where the
+ *                  "to" point's Z is finite and positive (and 1 / Z finite).
+ *   Yz <= 0 or Qz <= 0 at the linearisation point: the member adds nothing to that step and its point does not move; it adds
+ *   nothing to a cost either.
+ *   One step (Gauss-Newton, Schur complement, no damping): per point H_pp (3 x 3), g_p, H_cp (6 x 3) for the left perturbation
+ *   T <- Exp(delta) T, delta = [omega, v]; H_pp^-1 = adjugate / determinant.  Pivot rule: a point is free iff det H_pp is finite
+ *   and det > 1e-11 * H_pp[0][0] H_pp[1][1] H_pp[2][2]; otherwise it is held fixed for the step and its "to" pixel enters with
+ *   the 27 plain PnP terms of the level-aware form.  A free point adds H_cc - H_cp H_pp^-1 H_cp^T and g_c - H_cp H_pp^-1 g_p:
+ *   27 sums in the order of cslam_vis_pnp_dev's refinement (member k on lane k mod 256, a fixed shuffle tree per wave, the waves
+ *   added in wave order).  delta by the unpivoted LDL^T of pnp.h, T by the left perturbation, then per free point
+ *   Y_k <- Y_k - H_pp^-1 (g_p + H_cp^T delta) with the blocks of the same linearisation point.  A round stops after
+ *   ba_iterations steps, after a step with |delta| < 1e-10 (taken), or on a singular or non-finite system (not taken).
+ *   ba_rounds rounds of { steps; guard; recount }.  Guard: the weighted cost (sum of the weighted squared residuals, no
+ *   robust kernel) over the round's starting set, summed in the same fixed order, before and after the steps; if the cost
+ *   after is not finite or exceeds (1 + 1e-9) times the cost before, the round is discarded: T and the points go back to the
+ *   round's start (the slack is above the rounding of the two sums, so that at a converged start rounding does not decide).
+ *   Recount: a member stays iff Yz > 0, Qz > 0 and its squared pixel error is <= reproj_error^2 sigma2[la] in "from" and
+ *   <= reproj_error^2 sigma2[lb] in "to", with the refined Y and T.  The set only shrinks.
+ *   Status 0: at least min_inliers remain; 1: fewer, T is still the fit found.  A PnP status other than 0, ba_rounds == 0 or
+ *   ba_iterations == 0: nothing is adjusted, d_T, d_flags and the status are PnP's byte for byte, no refined points, costs NaN,
+ *   both set sizes = PnP's final inliers.
+ *   float64, no float atomics: the same input gives the same bytes alone, in any batch, in any order. */
+/* cslam_vis_ba_dev -- the adjustment alone (the step of computeTransformation after PnP, rgbd_handler.cpp:443-445, :519-520),
+ *   one workgroup per pair.  d_rows / d_row_off / d_count as for cslam_vis_pnp_dev: (row of "from", row of "to").  d_T0 [n, 16],
+ *   d_info0 [n, 8], d_flags0 [total rows]: what PnP wrote for these rows.  d_levels_from / d_levels_to int32 in the layout of
+ *   the keypoints, NULL = every level 0; the host copy of a given array is required and a level outside 0 .. 7 is refused
+ *   before any launch.  d_cameras_from / d_cameras_to [n, 4]; d_baselines / h_baselines [n, 2] (from, to), positive and finite.
+ *   Outputs, none of which may be a PnP array: d_T [n, 16]; d_info [n, 8] int32: status, set size in, set size out,
+ *   Gauss-Newton steps, rounds discarded, points held fixed (summed over the steps), PnP status, 0; d_flags [total rows] int32;
+ *   d_points [total rows, 3]: the refined point, in the "from" frame, of every row whose flag is 1, NaN elsewhere;
+ *   d_cost [n, 2]: the cost of the set at (T0, the "from" points), and the cost the last round ended with over its starting set. */
+int cslam_vis_ba_dev(const double *d_kp_from, const double *d_points_from, const int64_t *d_from_off, const double *d_kp_to,
+                     const double *d_points_to, const int64_t *d_to_off, const int32_t *d_levels_from, const int32_t *d_levels_to,
+                     const double *d_cameras_from, const double *d_cameras_to, const double *d_baselines, const int32_t *d_rows,
+                     const int64_t *d_row_off, const int32_t *d_count, const double *d_T0, const int32_t *d_info0,
+                     const int32_t *d_flags0, int n_pairs, double reproj_error, int min_inliers, int ba_iterations, int ba_rounds,
+                     double *d_T, int32_t *d_info, int32_t *d_flags, double *d_points, double *d_cost, const int64_t *h_from_off,
+                     const int64_t *h_to_off, const int64_t *h_row_off, const int32_t *h_levels_from, const int32_t *h_levels_to,
+                     const double *h_baselines, void *stream);
+/* cslam_vis_register_ba_dev -- the whole call of rgbd_handler.cpp:443-445 / :519-520 with the adjustment: match, PnP (the
+ *   uniform form where d_levels_to is NULL, the level-aware form otherwise; the PnP camera is d_cameras_to) and the adjustment,
+ *   chained on the stream with no host wait.  d_rows / d_count / d_T0 / d_info0 / d_flags0: what cslam_vis_register_dev (or
+ *   _levels_dev) writes; the rest as cslam_vis_ba_dev with d_row_off = d_from_off. */
+int cslam_vis_register_ba_dev(const uint8_t *d_desc_from, const double *d_kp_from, const double *d_points_from,
+                              const int64_t *d_from_off, const uint8_t *d_desc_to, const double *d_kp_to, const double *d_points_to,
+                              const int64_t *d_to_off, const int32_t *d_levels_from, const int32_t *d_levels_to,
+                              const double *d_cameras_from, const double *d_cameras_to, const double *d_baselines, int n_pairs,
+                              int desc_bytes, double nndr, int iterations, double reproj_error, int min_inliers, int refine_iterations,
+                              int refine_rounds, uint64_t seed, int ba_iterations, int ba_rounds, int32_t *d_rows, int32_t *d_count,
+                              double *d_T0, int32_t *d_info0, int32_t *d_flags0, double *d_T, int32_t *d_info, int32_t *d_flags,
+                              double *d_points, double *d_cost, const int64_t *h_from_off, const int64_t *h_to_off,
+                              const int32_t *h_levels_from, const int32_t *h_levels_to, const double *h_baselines, void *stream);
 
 /* ------------------------------------------------------------------------------------------------
  * Visual keyframes: corners, steered BRIEF-32 descriptors and 3D points from the image (csrc/feat.hip, csrc/feat.h).

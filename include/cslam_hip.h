@@ -624,8 +624,10 @@ int cslam_robust_graph_dev(const double *d_ms, const double *d_md, const int64_t
  *   equal ones the first that the search of the lowest root in the order meets.  A root's search uses nothing that other
  *   roots find (their sizes only skip whole roots that cannot hold a clique of the largest size), so the result does not
  *   depend on timing whenever the search completes.  node_budget: nodes (colourings) of one pair's search in all; when it
- *   runs out, or a branch gets deeper than 512 below its root, the pair returns the best clique found (never smaller than
- *   the greedy one) and certified = 0; a search that completes sets certified = 1.
+ *   runs out, or a branch would get 512 deep below its root, the pair returns the best clique found (never smaller than
+ *   the greedy one) and certified = 0; a search that completes sets certified = 1.  A branch 511 below its root, a clique
+ *   of 512, is the deepest that is searched; the best clique found counts what every root recorded until the search
+ *   ended, the one that ended it too.  A bit on the diagonal of d_adj is not an edge: no vertex is its own candidate.
  *   d_clique: ascending correspondence indices, capacity layout; d_clique_size, d_certified [n_pairs]; d_nodes: NULL or
  *   [n_pairs], the nodes used. */
 int cslam_robust_clique_dev(const uint64_t *d_adj, const int64_t *d_adj_off, const int32_t *d_deg, const int64_t *d_off,

@@ -3,9 +3,13 @@ graph, the maximum clique, GNC-TLS on the chain, per-axis TLS and the chained fi
 
 Neither TEASER++ nor its source is available where these tests run, so parity with TEASER++ itself is not pinned; this
 file follows the algorithm that the reference's `get_teaser_solver` parameters select (cslam/lidar_pr/icp_utils.py:68-83).
-The clique search is a small exact one of its own: Bron-Kerbosch with a pivot on Python ints used as bitsets.
+Two clique searches: `max_cliques`, a small exact one of its own (Bron-Kerbosch with a pivot on Python ints used as
+bitsets) that lists every maximum clique, and `clique_search`, the header's branch and bound restated rule by rule, which
+says WHICH of them the library returns, index for index.
 Also here: the generators of the tests and the measures of how close an input comes to a decision that rounding could turn.
 """
+import functools
+
 import numpy as np
 
 import fpfh_reference as fref
@@ -41,10 +45,11 @@ def to_words(adj):
     """The bit matrix of the library: [N, ceil(N / 64)] uint64, bit j of row i = bit j % 64 of word j // 64."""
     n = len(adj)
     w = (n + 63) // 64
-    out = np.zeros((n, w), dtype=np.uint64)
-    for j in range(n):
-        out[:, j // 64] |= adj[:, j].astype(np.uint64) << np.uint64(j % 64)
-    return out
+    if n == 0:
+        return np.zeros((0, 0), dtype=np.uint64)
+    padded = np.zeros((n, 64 * w), dtype=bool)
+    padded[:, :n] = adj
+    return np.packbits(padded, axis=1, bitorder="little").view("<u8").astype(np.uint64).reshape(n, w)
 
 
 def from_words(words, n):
@@ -53,7 +58,9 @@ def from_words(words, n):
 
 # ---- (b) the maximum clique -------------------------------------------------------------------------------------------
 def _rows_as_ints(adj):
-    return [int("".join("1" if x else "0" for x in row[::-1]), 2) if len(row) else 0 for row in np.asarray(adj, dtype=bool)]
+    """Row i as an int whose bit j is adj[i, j]."""
+    packed = np.packbits(np.asarray(adj, dtype=bool), axis=1, bitorder="little")
+    return [int.from_bytes(row.tobytes(), "little") for row in packed]
 
 
 def _bits(x):
@@ -119,11 +126,11 @@ def core_numbers(adj):
     return core
 
 
-def greedy_clique(adj):
+def greedy_clique(adj, core=None):
     """The lower bound of the search: the vertex of largest core number (the lowest index of equals), then again and
-    again the same choice among the common neighbours of those taken."""
+    again the same choice among the common neighbours of those taken.  `core`: the core numbers, where they are at hand."""
     adj = np.asarray(adj, dtype=bool)
-    core = core_numbers(adj)
+    core = core_numbers(adj) if core is None else core
     cand = np.ones(len(adj), dtype=bool)
     out = []
     while cand.any():
@@ -131,6 +138,94 @@ def greedy_clique(adj):
         out.append(v)
         cand &= adj[v]
     return sorted(out)
+
+
+def search_order(adj, core=None):
+    """The order of the search: the original indices in ascending (core number, index)."""
+    core = core_numbers(adj) if core is None else core
+    return np.lexsort((np.arange(len(core)), core))
+
+
+def _colour(nb, P, kmin):
+    """The members of P (a bitset of order positions) whose greedy colour exceeds kmin.  The colouring takes P in ascending
+    position, class by class: a class is the lowest member left and, again and again, the lowest one left that is adjacent
+    to none of the class so far.  Once kmin classes are full every member still left has a colour above kmin."""
+    if kmin <= 0:
+        return P
+    q, k = P, 0
+    while q:
+        k += 1
+        if k > kmin:
+            return q
+        c = q
+        while c:
+            low = c & -c
+            c &= ~(nb[low.bit_length() - 1] | low)
+            q ^= low
+    return 0
+
+
+def clique_search(adj, stack_depth=512, core=None):
+    """The clique that `cslam_robust_clique_dev` returns, by the rules of include/cslam_hip.h alone:
+    (clique as ascending original indices, certified, nodes).
+
+    Vertices are relabelled by `search_order`; g = the size of `greedy_clique`.  Roots go from the top of the order down
+    to the first whose core number + 1 is no more than g.  A root starts at own = g with R = [root] and P = its neighbours
+    later in the order.  At a node: an empty P records R when |R| > own (strictly: the first clique of a size stays) and
+    own becomes |R|; otherwise B = the members of P whose colour exceeds own - |R| (`_colour`; all of P when that is not
+    positive), fixed when the node is entered, and the members of B are branched on in ascending position, each leaving P
+    before its branch.  The winner is the largest clique recorded, of equal ones that of the lowest root, and the greedy
+    clique when no root beat g.  A push that would bring the depth below the root to `stack_depth` ends the whole search
+    uncertified: the answer is then the best clique recorded until there.
+    `nodes` counts every node entered with every such root searched.  The library also skips a root whose core number + 1
+    is below a size that another root has found already, so it reports this count or fewer.  `core`: the core numbers,
+    where they are at hand."""
+    adj = np.asarray(adj, dtype=bool)
+    n = len(adj)
+    if n == 0:
+        return [], True, 0
+    core = core_numbers(adj) if core is None else core
+    order = search_order(adj, core)
+    greedy = greedy_clique(adj, core)
+    g = len(greedy)
+    nb = _rows_as_ints(adj[np.ix_(order, order)])
+    top = core[order]
+    best_size, best, nodes, certified = g, None, 0, True
+    for root in range(n - 1, -1, -1):
+        if top[root] + 1 <= g or not certified:
+            break
+        own, found = g, None
+        R, saved = [root], []                                        # saved[d] = (P, B) of the node at depth d
+        P, B, enter = (nb[root] >> (root + 1)) << (root + 1), 0, True
+        while True:
+            if enter:
+                nodes += 1
+                enter = False
+                if not P:
+                    B = 0
+                    if len(R) > own:
+                        own, found = len(R), list(R)
+                else:
+                    B = _colour(nb, P, own - len(R))
+            if not B:
+                if not saved:
+                    break
+                P, B = saved.pop()
+                R.pop()
+                continue
+            low = B & -B
+            P ^= low
+            B ^= low
+            if len(R) >= stack_depth:                                # R holds the root and (depth below it) members
+                certified = False
+                break
+            saved.append((P, B))
+            P &= nb[low.bit_length() - 1]
+            R.append(low.bit_length() - 1)
+            enter = True
+        if own >= best_size and found is not None:                   # a lower root wins among equal sizes
+            best_size, best = own, found
+    return (greedy if best is None else sorted(int(order[v]) for v in best)), certified, nodes
 
 
 # ---- (c) rotation: GNC-TLS on the chain -------------------------------------------------------------------------------
@@ -301,6 +396,136 @@ def dense_case(seed=3, n=128, noise=0.5):
     ms = rng.uniform(-20.0, 20.0, (n, 3))
     _, T, _ = fref.moved_copy(ms[:1], seed)
     return ms, ms @ T[:3, :3].T + T[:3, 3] + noise * rng.standard_normal((n, 3))
+
+
+def gnp_case(seed, n, p):
+    """[n, n] bool: every pair an edge with probability p; symmetric, zero diagonal."""
+    rng = np.random.default_rng(11000 + seed)
+    adj = np.triu(rng.random((n, n), dtype=np.float32) < p, 1)
+    return adj | adj.T
+
+
+def decoy_case(parts, k, seed=None):
+    """(adj, planted): a cocktail-party graph on 2 * parts vertices (complete but for the perfect matching (2 i, 2 i + 1);
+    its maximum cliques have `parts` members and its core numbers are 2 * parts - 2) beside a disjoint clique of k (core
+    numbers k - 1): for parts < k <= 2 * parts - 2 (and one more without a seed: equal core numbers, the decoys have the lower
+    indices) the greedy clique sits among the decoys and the planted clique has to be found by the search, k - 1 levels
+    below its lowest root.  With a seed the vertices are relabelled by a permutation;
+    `planted` = the ascending indices of the clique of k."""
+    m = 2 * parts
+    adj = np.zeros((m + k, m + k), dtype=bool)
+    adj[:m, :m] = True
+    i = np.arange(parts)
+    adj[2 * i, 2 * i + 1] = adj[2 * i + 1, 2 * i] = False
+    adj[m:, m:] = True
+    np.fill_diagonal(adj, False)
+    at = np.arange(m + k) if seed is None else np.random.default_rng(12000 + seed).permutation(m + k)
+    out = np.zeros_like(adj)
+    out[np.ix_(at, at)] = adj
+    return out, np.sort(at[m:])
+
+
+def planted_gnp_case(seed, n, p, members):
+    """`gnp_case` with a clique planted on the original indices `members`."""
+    adj = gnp_case(seed, n, p)
+    m = np.asarray(members, dtype=np.int64)
+    adj[np.ix_(m, m)] = True
+    adj[m, m] = False
+    return adj
+
+
+def backtrack_case(fill=4096):
+    """(adj, A, second clique): a graph whose winner is met only after its root has come back from another branch, with
+    every set of that search in the second word of a lane (positions from `fill` on; the `fill` vertices below are isolated).
+    On the last 46 indices, all of core number 11 and so in index order: a complete bipartite graph on 11 + 11 vertices
+    (the greedy clique starts there and ends with 2), then r, d1 .. d10, x1, x2, a1 .. a11, where {r, d1 .. d10} is a
+    clique of 11, {d1 .. d10, x1, x2} one of 12 and A = {r, a1 .. a11} one of 12.  Root d1 meets its 12 first; the lower
+    root r first goes down d2, d1, ... to the 11, comes back to its own node, and only then goes down a2 to A, which wins
+    as the equal clique of the lower root."""
+    n = fill + 46
+    adj = np.zeros((n, n), dtype=bool)
+    idx = lambda a, k: list(range(fill + a, fill + a + k))
+    left, right, r, d, x, a = idx(0, 11), idx(11, 11), idx(22, 1), idx(23, 10), idx(33, 2), idx(35, 11)
+    adj[np.ix_(left, right)] = True
+    adj[np.ix_(right, left)] = True
+    for members in (r + d, d + x, r + a):
+        adj[np.ix_(members, members)] = True
+    np.fill_diagonal(adj, False)
+    return adj, r + a, d + x
+
+
+# The graphs on which the library's clique is compared with `clique_search` index for index.  The CPU tests assert what
+# makes them worth it (the greedy clique is too small, several maximum cliques exist, roots lie in both halves of a lane's
+# bitset); the GPU tests run the library on them.
+FAMILY_SEEDS = (0, 1)
+FAMILY = ((1, .5), (2, .5), (3, .5), (63, .5), (64, .5), (65, .5), (129, .3), (129, .5), (100, .7), (70, .9), (200, .2), (257, .1),
+          (192, .4))                                                 # (n, p): around one and two words, sparse to dense
+WIDE_PLANTED = (0, 63, 64, 4095, 4096, 4097, 4159, 4160, 8127, 8128, 8190, 8191)
+WIDE = {"4096/16": (4096, 16), "4097/16": (4097, 16), "8191/16": (8191, 16), "4160/40": (4160, 40), "8192/30": (8192, 30)}     # (n, mean degree)
+WIDE_ALL = tuple(WIDE) + ("8192/30+12", "K4097")
+MANY = 600
+
+
+class SearchCase:
+    """A graph and what the restatement makes of it: `adj`, `words` (the library's bit matrix), `core`, `greedy`, and
+    `clique`, `certified`, `nodes` = clique_search(adj)."""
+
+    def __init__(self, adj, planted=None):
+        self.adj, self.planted = adj, planted
+        self.words = to_words(adj)
+        self.core = core_numbers(adj)
+        self.greedy = greedy_clique(adj, self.core)
+        self.clique, self.certified, self.nodes = clique_search(adj, core=self.core)
+
+    @property
+    def want(self):
+        return self.clique, self.certified
+
+
+@functools.lru_cache(maxsize=None)
+def family_case(s, n, p):
+    return SearchCase(gnp_case(1000 * s + n, n, p))
+
+
+def family():
+    return [family_case(s, n, p) for s in FAMILY_SEEDS for n, p in FAMILY]
+
+
+@functools.lru_cache(maxsize=None)
+def wide_case(name):
+    if name == "K4097":
+        return SearchCase(~np.eye(4097, dtype=bool))
+    if name == "8192/30+12":
+        return SearchCase(planted_gnp_case(1, 8192, 30 / 8192, WIDE_PLANTED), np.array(WIDE_PLANTED))
+    n, degree = WIDE[name]
+    return SearchCase(gnp_case(n, n, degree / n))
+
+
+@functools.lru_cache(maxsize=None)
+def backtrack_search_case():
+    adj, first, second = backtrack_case()
+    return SearchCase(adj, np.array(first))
+
+
+@functools.lru_cache(maxsize=None)
+def decoy_search_case(k, seed=None):
+    return SearchCase(*decoy_case(500, k, seed))
+
+
+@functools.lru_cache(maxsize=None)
+def wide_pair(c):
+    """planted(5, 4200, 40), a pair whose bitsets need both words of a lane: (ms, md, inliers, graph, margin of the graph).
+    The point-based graph allocates [N, N, 3] float64 arrays: this is as large as a point case should get."""
+    ms, md, _, inliers = planted(5, 4200, 40)
+    adj, margin = consistency_graph(ms, md, c, return_margin=True)
+    return ms, md, inliers, adj, margin
+
+
+@functools.lru_cache(maxsize=None)
+def many_cases():
+    """MANY small graphs: n from 0 .. 40, p from .2, .5 and .8."""
+    rng = np.random.default_rng(13000)
+    return [SearchCase(gnp_case(20000 + i, int(rng.integers(0, 41)), float(rng.choice([.2, .5, .8])))) for i in range(MANY)]
 
 
 def lattice_case(n):

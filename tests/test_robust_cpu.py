@@ -1,6 +1,8 @@
-"""CPU: what the GPU comparisons of tests/test_robust_gpu.py rest on.  The C entry points of csrc/robust.hip exist and check
-their arguments before anything touches HIP, the module has no CPU path, the restatement of tests/robust_reference.py gives
-what hand-worked cases give, and the inputs of the GPU tests stay away from the decisions that rounding could turn."""
+"""CPU: what the GPU comparisons of tests/test_robust_gpu.py and tests/test_robust_clique_gpu.py rest on.  The C entry
+points of csrc/robust.hip exist and check their arguments before anything touches HIP, the module has no CPU path, the
+restatement of tests/robust_reference.py gives what hand-worked cases give, the inputs of the GPU tests stay away from the
+decisions that rounding could turn, and the restated clique search returns the maximum clique that the header's rule names
+on graphs where that rule decides something."""
 import ctypes
 import os
 
@@ -177,6 +179,151 @@ def test_clique_search_agrees_with_networkx():
     sizes = [len(c) for c in nx.find_cliques(nx.from_numpy_array(adj))]
     size, cliques = ref.max_cliques(adj)
     assert size == max(sizes) and len(cliques) == sizes.count(size)
+
+
+def lowest_position(case, clique):
+    """The lowest position in the order of the search among the members of a clique: its root."""
+    position = np.empty(len(case.adj), dtype=np.int64)
+    position[ref.search_order(case.adj, case.core)] = np.arange(len(case.adj))
+    return int(position[np.asarray(clique, dtype=np.int64)].min())
+
+
+def check_winner(case, nx=None):
+    """What the header's rule promises of `clique_search`: a maximum clique; the greedy one when that is one; otherwise one
+    whose root no other maximum clique undercuts.  Returns (maximum size, number of maximum cliques)."""
+    size, cliques = ref.max_cliques(case.adj)
+    assert case.certified and case.clique in cliques
+    if size == len(case.greedy):
+        assert case.clique == case.greedy
+    else:
+        assert lowest_position(case, case.clique) == min(lowest_position(case, c) for c in cliques)
+    if nx is not None and len(case.adj):
+        assert size == nx.max_weight_clique(nx.from_numpy_array(case.adj), weight=None)[1]     # its own branch and bound
+    return size, len(cliques)
+
+
+def test_restated_search_on_cases_worked_by_hand():
+    # two triangles {0, 1, 2} and {3, 4, 5} joined by the edge 2 - 3, and the pendant 6 on vertex 0: core numbers 2 but for
+    # the pendant's 1; the greedy clique is the first triangle, nothing beats it, and every root is one node
+    g = np.zeros((7, 7), dtype=bool)
+    for i, j in ((0, 1), (0, 2), (1, 2), (3, 4), (3, 5), (4, 5), (2, 3), (0, 6)):
+        g[i, j] = g[j, i] = True
+    assert ref.core_numbers(g).tolist() == [2, 2, 2, 2, 2, 2, 1] and ref.search_order(g).tolist() == [6, 0, 1, 2, 3, 4, 5]
+    assert ref.clique_search(g) == ([0, 1, 2], True, 0)                # core + 1 = 3 <= g = 3: no root is searched
+    # the 5-cycle 0-1-2-3-4 with the chords 1 - 3 and 2 - 4: core numbers 2, the order is the indices, the greedy clique
+    # {0, 1} starts at the lowest index and misses both triangles.  Roots 4, 3 and 0 are one node each; root 2 meets
+    # {2, 4, 3} and root 1 meets {1, 3, 2} in three nodes each: equal sizes, the lower root wins
+    g = np.zeros((5, 5), dtype=bool)
+    for i, j in ((0, 1), (1, 2), (2, 3), (3, 4), (4, 0), (1, 3), (2, 4)):
+        g[i, j] = g[j, i] = True
+    assert ref.core_numbers(g).tolist() == [2] * 5 and ref.greedy_clique(g) == [0, 1]
+    assert ref.max_cliques(g) == (3, [[1, 2, 3], [2, 3, 4]]) and ref.clique_search(g) == ([1, 2, 3], True, 9)
+    # the colouring: a path 0 - 1 - 2 has the classes {0, 2} and {1}; only vertex 1 has a colour above 1
+    nb = ref._rows_as_ints(np.array([[0, 1, 0], [1, 0, 1], [0, 1, 0]], dtype=bool))
+    assert ref._colour(nb, 0b111, 1) == 0b010 and ref._colour(nb, 0b111, 0) == 0b111 and ref._colour(nb, 0b111, 2) == 0
+    assert ref._colour(nb, 0b101, 1) == 0 and ref._colour(nb, 0b011, 1) == 0b010
+    # the depth: a clique of 5 beside three decoy pairs, in which the greedy clique starts, needs 4 levels below its root
+    adj, planted = ref.decoy_case(3, 5)
+    assert len(ref.greedy_clique(adj)) == 3 and planted.tolist() == [6, 7, 8, 9, 10]
+    assert ref.clique_search(adj, stack_depth=5)[:2] == ([6, 7, 8, 9, 10], True)
+    assert ref.clique_search(adj, stack_depth=4)[:2] == ([7, 8, 9, 10], False)       # root 7 found its 4 before root 6 gave up
+    adj2, planted2 = ref.decoy_case(3, 5, seed=1)
+    assert not np.array_equal(adj, adj2) and ref.clique_search(adj2)[0] == planted2.tolist() and ref.is_clique(adj2, planted2)
+    assert ref.gnp_case(3, 50, .5).diagonal().sum() == 0 and np.array_equal(ref.gnp_case(3, 50, .5), ref.gnp_case(3, 50, .5).T)
+    assert ref.clique_search(np.zeros((0, 0), dtype=bool)) == ([], True, 0)
+
+
+def test_restated_search_on_the_random_family():
+    """On every graph of the family the restated search returns the maximum clique that the header's rule names, and the
+    family is one on which that rule decides something: the greedy clique is too small on two thirds of the graphs, more
+    than one maximum clique exists on half, and no search comes near the node budget."""
+    try:
+        import networkx as nx
+    except ImportError:
+        nx = None
+    from cslam_amd.lidar_pr import icp_utils as u
+    cases = ref.family()
+    assert len(cases) == 26
+    smaller = several = 0
+    for case in cases:
+        size, count = check_winner(case, nx)
+        smaller += len(case.greedy) < size
+        several += count > 1
+    nodes = max(case.nodes for case in cases)
+    print("family: greedy smaller on %d of %d, several maximum cliques on %d, at most %d nodes, largest clique %d"
+          % (smaller, len(cases), several, nodes, max(len(case.clique) for case in cases)))
+    assert 3 * smaller >= 2 * len(cases) and 2 * several >= len(cases)
+    assert nodes < u.ROBUST_DEFAULT_NODE_BUDGET // 16
+
+
+def test_restated_search_at_the_depth_limit():
+    """A clique of 512 beside 500 decoy pairs is found 511 levels below its root, which is as deep as a search may go; one
+    of 513 would need another level: the search ends uncertified with what the roots above had recorded."""
+    from cslam_amd.lidar_pr import icp_utils as u
+    assert u.ROBUST_STACK_DEPTH == 512
+    case = ref.decoy_search_case(512)
+    print("decoy_case(500, 512): greedy %d, clique %d, %d nodes" % (len(case.greedy), len(case.clique), case.nodes))
+    assert len(case.greedy) == 500 and case.certified and case.clique == case.planted.tolist() and case.nodes < 10 ** 5
+    case = ref.decoy_search_case(513)
+    assert len(case.greedy) == 500 and not case.certified and len(case.clique) >= 500 and ref.is_clique(case.adj, case.clique)
+    assert case.clique == case.planted.tolist()[1:]                  # the root above the lowest one found its 512
+    for seed, k in ((1, 512), (2, 513)):                             # relabelled, as the GPU tests run them
+        adj, planted = ref.decoy_case(500, k, seed)
+        assert len(ref.greedy_clique(adj)) == 500 and ref.is_clique(adj, planted) and len(planted) == k
+
+
+@pytest.mark.parametrize("name", ref.WIDE_ALL)
+def test_restated_search_on_the_wide_graphs(name):
+    """More than 4096 vertices: a lane of the search holds two words of every set.  The winner is a maximum clique by the
+    header's rule, every vertex is a root that is searched, and roots lie in both halves."""
+    case = ref.wide_case(name)
+    n = len(case.adj)
+    if name == "K4097":                                              # listing its one clique would recurse 4097 deep
+        assert case.clique == list(range(n)) and case.certified and case.nodes == 0 and case.greedy == case.clique
+        return
+    size, count = check_winner(case)
+    print("%s: greedy %d, maximum %d (%d of them), %d nodes, core numbers %d .. %d" % (name, len(case.greedy), size, count, case.nodes,
+                                                                                         case.core.min(), case.core.max()))
+    assert n >= 4096 and (case.core + 1 > len(case.greedy)).all()    # every vertex is a root, in both halves of the order
+    assert case.nodes >= n
+    if case.planted is not None:
+        assert count == 1 and case.clique == case.planted.tolist() and len(case.greedy) < size
+        position = np.argsort(ref.search_order(case.adj, case.core))[case.planted]
+        assert position.min() < 4096 <= position.max()               # the clique itself spans both halves
+    else:
+        assert len(case.greedy) < size and count > 1
+
+
+def test_restated_search_comes_back_to_a_node_in_the_second_words():
+    """`backtrack_case`: the winner is met after the root's first branch has ended elsewhere, so a search that loses the
+    candidates of a node it comes back to, above position 4096, returns another clique."""
+    case = ref.backtrack_search_case()
+    adj, first, second = ref.backtrack_case()
+    n, s = len(adj), len(adj) - 46
+    assert s == 4096 and case.core[:s].max() == 0 and (case.core[s:] == 11).all()
+    assert ref.search_order(adj, case.core).tolist() == list(range(n))              # positions are indices
+    assert ref.max_cliques(adj[s:, s:]) == (12, sorted([[v - s for v in first], [v - s for v in second]]))
+    assert len(case.greedy) == 2 and case.certified and case.clique == first and min(first) < min(second)
+    nb = ref._rows_as_ints(adj)
+    root = first[0]
+    B = ref._colour(nb, (nb[root] >> (root + 1)) << (root + 1), len(case.greedy) - 1)
+    assert (B & -B).bit_length() - 1 not in first                    # the first branch of the winning root leaves the winner
+
+
+def test_input_conditions_of_the_wide_pair():
+    ms, md, inliers, adj, margin = ref.wide_pair(C_PLANTED)
+    clique, unique = ref.max_clique(adj)
+    print("planted(5, 4200, 40): graph margin %.2e, mean degree %.1f, greedy %d" % (margin, adj.sum(axis=1).mean(), len(ref.greedy_clique(adj))))
+    assert margin >= MARGIN and unique and clique == inliers.tolist() and len(ms) > 4096
+    assert ref.clique_search(adj)[:2] == (clique, True)
+
+
+def test_many_small_graphs_cover_every_size():
+    cases = ref.many_cases()
+    sizes = {len(case.adj) for case in cases}
+    assert len(cases) == ref.MANY > 512 and sizes == set(range(41))
+    assert all(case.certified and ref.is_clique(case.adj, case.clique) for case in cases)
+    assert sum(len(case.greedy) < len(case.clique) for case in cases) >= 50
 
 
 def test_input_conditions_of_the_graph_and_clique_comparisons():

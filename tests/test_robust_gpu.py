@@ -1,8 +1,11 @@
 """GPU: the robust coarse fit (csrc/robust.hip through cslam_amd.lidar_pr.icp_utils) against the float64 restatement of
 its rules in tests/robust_reference.py, stage by stage and chained.  The shapes are the smallest at which the kernels can
-still go wrong: sizes around a 64-bit word, a wave and the LDS chunk, more than one workgroup, both halves of a lane's
-bitset.  tests/test_robust_cpu.py checks that the decisions compared here (edges, weight bands, stopping) do not hang on
-the last bits, and that the planted cliques are the only maximum ones."""
+still go wrong: sizes around a 64-bit word, a wave and the LDS chunk, more than one workgroup.  No graph here has more
+than 1000 vertices, so a lane of the clique search holds one word of every set, and on the planted cases the greedy clique
+already is the maximum one: the search itself (which clique wins, more than 4096 vertices, widths mixed in a call, one
+wave per pair, the depth limit) is compared index for index in tests/test_robust_clique_gpu.py.
+tests/test_robust_cpu.py checks that the decisions compared here (edges, weight bands, stopping) do not hang on the last
+bits, and that the planted cliques are the only maximum ones."""
 import numpy as np
 import pytest
 
